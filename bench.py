@@ -4,12 +4,19 @@
 resident in HBM) -> repeat-pad to feat_len 750 -> ResNet-18 forward -> OC-Softmax
 (ang_iso) -> backward -> [RCCL all-reduce] -> Adam + SGD, fp32, batch 64 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
+A plain run sets up, runs W warm-up steps, times ONE window of exactly K steps (value and
+ms_per_step come from it), writes the last timed step's results with --dump-outputs, and
+prints ONE JSON line on rank 0.  --full adds the other measurements:
+  "windowed":     the same configuration again under the stability protocol (10-step windows
+                  until steady, then --windows windows of max(K, 50) steps, median) with
+                  clock / power samples
   "roofline":     dominant kernel (f32-MFMA implicit-GEMM conv) timed with HIP events on
-                  its launch stream: algorithmic FLOPs / time vs the 157.3 TFLOP/s f32 peak
+                  its launch stream: algorithmic FLOPs / time vs the 157.3 TFLOP/s f32 peak,
+                  HBM traffic from rocprofv3 --pmc child passes
+  "configs":      ECAPA-TDNN-512 bf16, both models at T = 401, the Dataset-fed pipeline
   "cpu_baseline": the CPU oracle (a PyTorch-CPU port of the reference path, pinned to the
                   reference by tests/golden) timed on this box's host cores on a bounded
                   sample of BASELINE.json configs[0].
@@ -93,6 +100,28 @@ def smi_sample(device_index=0):
     except Exception as exc:  # noqa: BLE001
         out["error"] = "%s: %s" % (type(exc).__name__, exc)
     return out
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, loss, neg, trainer):
+    """--dump-outputs: what the last timed step handed back and left behind, as float32 .npy files - loss.npy,
+    neg_scores.npy (Trainer.step's return values) and state.npy (every floating tensor of the model's and the loss
+    module's state_dicts after the optimiser step, flattened in state_dict order).  The state is a fixed seeded
+    sample of its elements when the whole would exceed DUMP_LIMIT_BYTES."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": loss.detach().reshape(1), "neg_scores": neg.detach().reshape(-1)}
+    sds = (trainer.model.state_dict(), trainer.loss.state_dict())
+    state = torch.cat([t.detach().reshape(-1).float() for sd in sds for t in sd.values() if t.is_floating_point()])
+    room = (DUMP_LIMIT_BYTES - 4 * sum(v.numel() for v in out.values())) // 4 - 1024  # (.npy headers)
+    if state.numel() > room:
+        idx = torch.randperm(state.numel(), generator=torch.Generator().manual_seed(688))[:room].sort().values
+        state = state[idx.to(state.device)]
+    out["state"] = state
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def synth_batch(step, rank, device):
@@ -232,8 +261,8 @@ def roofline_leg(trainer, batches):
 
 
 def pmc_traffic_leg(model_name, family, argv_extra, timeout_s=170):
-    """HBM-side bytes per launch of the dominant kernel, measured in THIS run: two child runs of this script (2 timed
-    steps, no roofline / CPU legs) under ``rocprofv3 --kernel-trace --pmc FETCH_SIZE`` and ``--pmc WRITE_SIZE`` -
+    """HBM-side bytes per launch of the dominant kernel, measured in THIS run: two plain child runs of this script
+    (1 warm-up + 2 timed steps) under ``rocprofv3 --kernel-trace --pmc FETCH_SIZE`` and ``--pmc WRITE_SIZE`` -
     separate passes and the unit / gfx950 corrections as MI355X_MICROARCH.md prescribes (counters are KB;
     FETCH_SIZE tallies 128-byte requests at 64 B on gfx950: doubled; WRITE_SIZE as reported).  Returns a dict for
     the roofline object, with traffic = None and the reason when rocprofv3 is missing or a pass fails."""
@@ -249,8 +278,7 @@ def pmc_traffic_leg(model_name, family, argv_extra, timeout_s=170):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         with tempfile.TemporaryDirectory(dir="/tmp") as d:
             cmd = [prof, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "pmc", "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--model", model_name, "--steps", "2", "--warmup", "1",
-                   "--no-cpu-baseline", "--no-roofline", "--no-extra-configs", "--no-pmc", "--plain-timing"] + argv_extra
+                   os.path.join(ROOT, "bench.py"), "--model", model_name, "--steps", "2", "--warmup", "1"] + argv_extra
             env = dict(os.environ, TMPDIR="/tmp", PYTHONPATH=ROOT)
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -384,20 +412,30 @@ def main():
     ap.add_argument("--sync-each-step", action="store_true",
                     help="read the loss back on the host after every timed step, as the reference's loop does "
                          "(main_train.py:479-481 writes loss.item() to train_loss.log per iteration)")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of the headline configuration (median reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (loss, neg_scores, the model and loss state after the step) "
+                         "as float32 DIR/<name>.npy, at most 64 MB in all; the inputs depend on the arguments alone")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline: the windowed protocol, roofline + PMC traffic, "
+                         "exposed communication (N > 1), the extra configurations, the Dataset-fed leg, the CPU baseline")
+    ap.add_argument("--windows", type=int, default=5, help="--full: windows of the windowed protocol (median reported)")
     ap.add_argument("--plain-timing", action="store_true",
-                    help="the contract's literal protocol: W warm-up steps and ONE window of exactly K steps, no stability "
-                         "warm-up (what the rocprofv3 --pmc child passes and the tests run)")
+                    help="--full: skip the windowed protocol (and with it the Dataset-fed leg and the A-B-A repeat)")
     ap.add_argument("--from-dataset", action="store_true",
-                    help="also time the configuration fed by DataLoader(ASVspoof2019 over a SyntheticSource) -> pinned PCM -> "
-                         "copy stream -> Trainer.step (reported under configs.*_from_dataset; part of the default run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="--full: also time the configuration fed by DataLoader(ASVspoof2019 over a SyntheticSource) -> "
+                         "pinned PCM -> copy stream -> Trainer.step (reported under configs.*_from_dataset; part of every "
+                         "--full run without --plain-timing)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline leg")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic (N = 1, rank 0 only)")
+                    help="--full: skip the two rocprofv3 --pmc child passes that measure roofline.traffic (N = 1, rank 0 only)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="default run only: skip the ECAPA-TDNN-512 bf16 leg (BASELINE configs[2]) reported under 'configs'")
+                    help="--full: skip the ECAPA-TDNN-512 bf16 and T = 401 legs reported under 'configs'")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.from_dataset and not args.full:
+        ap.error("--from-dataset is one of the --full measurements: add --full")
 
     from asvspoof2021_air_amd import dist as air_dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -424,10 +462,12 @@ def main():
             td.barrier()
         torch.cuda.synchronize()
 
-    def run_config(model_name, dtype, batch, steps, warmup, augment, want_roofline, nwin=3):
-        """One configuration: W warm-up steps, the stability warm-up, `nwin` timed windows (barrier + synchronize
-        fences, MAX over ranks), then the instrumented roofline steps.  Returns (model, dict, retime) - retime(nwin)
-        times the same trainer again later in the process (the A-B-A repeat of the headline)."""
+    def run_config(model_name, dtype, batch, steps, warmup, augment, want_roofline, nwin=3, dump_dir=None):
+        """One configuration: W warm-up steps and ONE timed window of exactly K steps (barrier + synchronize fences,
+        MAX over ranks) - the headline; the last step's results go to `dump_dir`.  With --full also the windowed
+        protocol, the exposed communication (world > 1) and the instrumented roofline steps.  Returns (model, dict,
+        retime, from_dataset) - retime(nwin) runs the windowed protocol on the same trainer again later in the process
+        (the A-B-A repeat)."""
         global BATCH
         torch.manual_seed(688)
         if model_name == "resnet":
@@ -465,14 +505,15 @@ def main():
         nrun = [0]
 
         def window(n):
-            """n steps between barrier + synchronize fences; (seconds, host-issue seconds, last loss), MAX over ranks."""
+            """n steps between barrier + synchronize fences; (seconds, host-issue seconds, the last step's (loss,
+            neg_scores)), MAX over ranks."""
             fence()
             t0 = time.perf_counter()
             last = None
             for i in range(n):
-                last, _ = trainer.step(*batches[i % nb])
+                last = trainer.step(*batches[i % nb])
                 if args.sync_each_step:
-                    last.item()
+                    last[0].item()
             t_host = time.perf_counter() - t0  # all launches issued (the host side of the step; the GPU is behind)
             fence()
             dt = time.perf_counter() - t0
@@ -483,48 +524,40 @@ def main():
                 dt = float(t.item())
             return dt, t_host, last
 
-        def measure(nwin, first=True):
-            """The timed part: (result dict, seconds of one median step)."""
-            if first:
-                if trainer.use_graph:  # two eager steps + the capture happen before the W warm-up steps, never inside the timed ones
-                    for i in range(3):
-                        trainer.step(*batches[i % nb])
-                    nrun[0] += 3
-                for i in range(warmup):
-                    trainer.step(*batches[i % nb])
-                nrun[0] += warmup
-            smi0 = smi_sample(local) if (rank == 0 and not args.plain_timing) else None
-            timing = {"protocol": "plain"}
-            if args.plain_timing:
-                # the contract's literal protocol: W warm-up steps, ONE window of exactly K steps (PMC child passes, tests)
-                wsteps = steps
-                wins = [window(steps)]
-            else:
-                # Round 5 (VERDICT r4 item 9: the round-4 headline was taken 0.1 s after start on a cold box and read 11 %
-                # low).  Warm-up by TIME and STABILITY behind the W steps: 10-step windows until >= 2 s have been run and
-                # three consecutive windows agree within 1 % (capped at 12 s; the decision uses the all-reduced MAX, so
-                # every rank leaves the loop together).  Then `nwin` windows of max(K, 50) steps; value = the MEDIAN window.
-                settle, t_settle = [], 0.0
-                while True:
-                    dt, _, _ = window(10)
-                    settle.append(1e3 * dt / 10)
-                    t_settle += dt
-                    last3 = settle[-3:]
-                    stable = len(last3) == 3 and (max(last3) - min(last3)) <= 0.01 * min(last3)
-                    if (t_settle >= 2.0 and stable) or t_settle >= 12.0:
-                        break
-                wsteps = max(steps, 50)
-                wins = [window(wsteps) for _ in range(nwin)]
-                timing = {"protocol": "W warm-up steps, then 10-step windows until >= 2 s and three consecutive windows within "
-                                      "1 %% (cap 12 s), then %d windows of max(K, 50) = %d steps between barrier + synchronize "
-                                      "fences; value and ms_per_step are the MEDIAN window" % (nwin, wsteps),
-                          "settle_windows_ms_per_step": [round(v, 3) for v in settle], "settle_s": round(t_settle, 2),
-                          "settled": bool(stable)}
+        def launch_mode():
+            if trainer.use_graph and trainer._graph is not None and trainer._graph.get("segments"):
+                return ("hipGraph replay (%d segments, a bucket's all-reduce between two replays) + optimiser launches"
+                        % len(trainer._graph["segments"]))
+            return "hipGraph replay (one chain) + optimiser launches" if trainer.use_graph else "eager"
+
+        def windowed(nwin):
+            """--full: the stability protocol on the warm trainer; a dict of its median window and how it was taken."""
+            smi0 = smi_sample(local) if rank == 0 else None
+            # Round 5 (VERDICT r4 item 9: the round-4 headline was taken 0.1 s after start on a cold box and read 11 %
+            # low).  Warm-up by TIME and STABILITY: 10-step windows until >= 2 s have been run and three consecutive
+            # windows agree within 1 % (capped at 12 s; the decision uses the all-reduced MAX, so every rank leaves the
+            # loop together).  Then `nwin` windows of max(K, 50) steps; value = the MEDIAN window.
+            settle, t_settle = [], 0.0
+            while True:
+                dt, _, _ = window(10)
+                settle.append(1e3 * dt / 10)
+                t_settle += dt
+                last3 = settle[-3:]
+                stable = len(last3) == 3 and (max(last3) - min(last3)) <= 0.01 * min(last3)
+                if (t_settle >= 2.0 and stable) or t_settle >= 12.0:
+                    break
+            wsteps = max(steps, 50)
+            wins = [window(wsteps) for _ in range(nwin)]
+            timing = {"protocol": "after the headline window: 10-step windows until >= 2 s and three consecutive windows "
+                                  "within 1 %% (cap 12 s), then %d windows of max(K, 50) = %d steps between barrier + "
+                                  "synchronize fences; value and ms_per_step are the MEDIAN window" % (nwin, wsteps),
+                      "settle_windows_ms_per_step": [round(v, 3) for v in settle], "settle_s": round(t_settle, 2),
+                      "settled": bool(stable)}
             per = sorted(1e3 * w[0] / wsteps for w in wins)
             med = per[len(per) // 2] if len(per) % 2 else 0.5 * (per[len(per) // 2 - 1] + per[len(per) // 2])
             dt = med * 1e-3 * wsteps
             t_host = sorted(w[1] for w in wins)[len(wins) // 2]
-            last = wins[-1][2]
+            last = wins[-1][2][0]
             timing.update({"steps_per_window": wsteps, "windows_ms_per_step": [round(1e3 * w[0] / wsteps, 3) for w in wins],
                            "min_ms_per_step": round(per[0], 3), "max_ms_per_step": round(per[-1], 3),
                            "spread": round((per[-1] - per[0]) / med, 4)})
@@ -556,21 +589,32 @@ def main():
                             "how": "s_memtime / 100 MHz wall clock sampled by one wave on a side stream beside %d untimed steps" % n_probe}
                 except Exception as e:  # instrumentation only
                     timing["core_clock_mhz_during_steps"] = {"error": repr(e)[:200]}
-            steps_timed = wsteps
-            res = {"value": round(world * BATCH * steps_timed / dt, 2), "unit": "utt/s", "steps": steps, "warmup": warmup,
-                   "ms_per_step": round(1e3 * dt / steps_timed, 3), "per_gpu_batch": BATCH, "global_batch": world * BATCH,
-                   "final_loss": round(float(last.item()), 5), "host_issue_ms_per_step": round(1e3 * t_host / steps_timed, 3),
-                   "launch": (("hipGraph replay (%d segments, a bucket's all-reduce between two replays) + optimiser launches"
-                               % len(trainer._graph["segments"])) if (trainer.use_graph and trainer._graph is not None
-                                                                      and trainer._graph.get("segments"))
-                              else "hipGraph replay (one chain) + optimiser launches" if trainer.use_graph else "eager"),
-                   "steps_timed_per_window": steps_timed, "windows": len(wins),
-                   "timing": timing, "steps_run_total": nrun[0]}
-            return res, dt / steps_timed
+            return {"value": round(world * BATCH * wsteps / dt, 2), "unit": "utt/s", "ms_per_step": round(1e3 * dt / wsteps, 3),
+                    "final_loss": round(float(last.item()), 5), "host_issue_ms_per_step": round(1e3 * t_host / wsteps, 3),
+                    "steps_timed_per_window": wsteps, "windows": len(wins), "timing": timing}
 
-        res, step_s = measure(nwin)
+        if trainer.use_graph:  # two eager steps + the capture happen before the W warm-up steps, never inside the timed ones
+            for i in range(3):
+                trainer.step(*batches[i % nb])
+            nrun[0] += 3
+        for i in range(warmup):
+            trainer.step(*batches[i % nb])
+        nrun[0] += warmup
+        # the headline: ONE window of exactly K steps
+        dt, t_host, (last_loss, last_neg) = window(steps)
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, last_loss, last_neg, trainer)
+        step_s = dt / steps
+        res = {"value": round(world * BATCH * steps / dt, 2), "unit": "utt/s", "steps": steps, "warmup": warmup,
+               "ms_per_step": round(1e3 * step_s, 3), "per_gpu_batch": BATCH, "global_batch": world * BATCH,
+               "final_loss": round(float(last_loss.item()), 5), "host_issue_ms_per_step": round(1e3 * t_host / steps, 3),
+               "launch": launch_mode(), "steps_timed_per_window": steps, "windows": 1,
+               "timing": {"protocol": "W warm-up steps (behind the two eager steps + capture of a hipGraph replay), then ONE "
+                                      "window of exactly K steps between barrier + synchronize fences"}}
+        if args.full and not args.plain_timing:
+            res["windowed"] = windowed(nwin)
         comm = None
-        if world > 1:
+        if args.full and world > 1:
             # exposed communication: the same steps without the gradient exchange (no buckets from inside
             # backward, no all-reduce; replicas drift apart, which no later figure depends on), MAX over ranks
             arena = model.arena()
@@ -668,19 +712,20 @@ def main():
                    "corpus": "%d synthetic 4 s utterances (synth.py), generated once in %.1f s, shuffled every epoch" % (nutt, gen_s),
                    "pipeline": "ASVspoof2019(SyntheticSource, return_pcm='batch').collate_fn -> pinned (B, L) -> "
                                "DevicePrefetcher (copy stream, depth 2) -> Trainer.step (fused LFCC inside the replay)",
-                   "vs_resident": round((world * BATCH * 1e3 / med) / res["value"], 4)}
+                   "vs_resident": round((world * BATCH * 1e3 / med) / res.get("windowed", res)["value"], 4)}
             return out
 
-        return model, res, (lambda n: measure(n, first=False)[0]), from_dataset
+        return model, res, windowed, from_dataset
 
     model, main_res, retime_main, dataset_main = run_config(args.model, args.dtype, args.batch, args.steps, args.warmup,
-                                                            args.augment, not args.no_roofline, nwin=args.windows)
+                                                            args.augment, args.full and not args.no_roofline,
+                                                            nwin=args.windows, dump_dir=args.dump_outputs)
     roofline = main_res.pop("roofline", None)
     main_batch = BATCH
-    # BASELINE configs[2] (ECAPA-TDNN-512, bf16 compute, batch 128 per GPU) rides along in the default run so
-    # that the driver's bench line carries a measured number for it too
+    # BASELINE configs[2] (ECAPA-TDNN-512, bf16 compute, batch 128 per GPU) rides along in a --full run so
+    # that its bench line carries a measured number for it too
     extra = {}
-    if args.model == "resnet" and not args.no_extra_configs and args.batch == 0 and not args.augment:
+    if args.full and args.model == "resnet" and not args.no_extra_configs and args.batch == 0 and not args.augment:
         # (the headline's model and trainer stay alive for the A-B-A repeat at the end: 288 GB of HBM)
         # (a failure of this additional leg must not cost the headline line; with world > 1 every rank takes the
         # same path through its collectives, so an exception there is not caught - it would desynchronise the ranks)
@@ -731,7 +776,7 @@ def main():
             e["roofline"].update(pmc_traffic_leg("ecapa", e["roofline"]["kernel"], ["--feat-len", str(args.feat_len)]))
 
     # the headline configuration fed through the Dataset surface (DataLoader -> pinned PCM -> copy stream -> Trainer.step)
-    if (args.from_dataset or (extra and not args.plain_timing)) and not args.augment:
+    if args.full and (args.from_dataset or (extra and not args.plain_timing)) and not args.augment:
         BATCH = main_batch
         try:
             extra["%s_from_dataset" % ("resnet_f32_b64" if args.model == "resnet" else "ecapa_b128")] = dataset_main()
@@ -739,14 +784,14 @@ def main():
             if world > 1:
                 raise
             extra["from_dataset"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    # A-B-A: the headline configuration once more at the END of the process (same trainer, no warm-up beyond the
-    # stability windows), so that a drift between the first and the last leg of the process shows in the record
+    # A-B-A: the windowed protocol of the headline configuration once more at the END of the process (same trainer, no
+    # warm-up beyond the stability windows), so that a drift between the first and the last leg shows in the record
     repeat = None
-    if not args.plain_timing and extra:
+    if args.full and not args.plain_timing and extra:
         BATCH = main_batch
         r2 = retime_main(3)
         repeat = {k: r2[k] for k in ("value", "ms_per_step", "host_issue_ms_per_step", "timing")}
-        repeat["vs_first"] = round(r2["value"] / main_res["value"], 4)
+        repeat["vs_first"] = round(r2["value"] / main_res["windowed"]["value"], 4)
     if rank == 0:
         line = {
             "metric": "utterances/sec (LFCC+ResNet-OCSoftmax train step, 4 s@16 kHz)",
@@ -762,8 +807,8 @@ def main():
             "final_loss": main_res["final_loss"],
             "host_issue_ms_per_step": main_res["host_issue_ms_per_step"],
             "launch": main_res["launch"],
-            # `steps` echoes --steps (the contract); the timed region is `windows` windows of `steps_timed_per_window` steps
-            # (= max(K, 50) unless --plain-timing), value / ms_per_step = the median window
+            # value / ms_per_step: ONE window of exactly `steps` timed steps (--full reports its windowed protocol under
+            # `windowed`)
             "steps_timed_per_window": main_res["steps_timed_per_window"], "windows": main_res["windows"],
             "timing": main_res["timing"], "steps_run_total": main_res["steps_run_total"],
             "sync_each_step": bool(args.sync_each_step),
@@ -782,13 +827,15 @@ def main():
                            "fp32 compute (the reference's arithmetic; configs[2] itself is the bf16 variant)"))
         if args.augment:
             line["config"]["workload"] += "; + on-the-fly IR convolution (1024 taps) of every utterance ahead of LFCC"
+        if "windowed" in main_res:
+            line["windowed"] = main_res["windowed"]
         if roofline is not None:
             line["roofline"] = roofline
         if extra:
             line["configs"] = extra
         if repeat is not None:
             line["headline_repeat_at_end"] = repeat
-        if world == 1 and not args.no_cpu_baseline and args.model == "resnet":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "resnet":
             try:
                 line["cpu_baseline"] = cpu_baseline_leg()
             except Exception as exc:  # noqa: BLE001  (the headline line still goes out)

@@ -258,8 +258,8 @@ def test_bench_two_ranks_on_one_gpu(mode):
         env["AIR_GRAPH"] = "0"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "8", "--plain-timing"]  # (gloo moves 49.8 MB per step through the host: one
-    # window of K steps instead of the settle + 5 x 50-step protocol); the roofline leg runs on every rank
+           "--warmup", "1", "--batch", "8", "--full", "--plain-timing"]  # (gloo moves 49.8 MB per step through the
+    # host: no windowed protocol); --full: the roofline leg runs on every rank, the exposed communication is measured
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _bench_line(r, out_json)
@@ -295,7 +295,7 @@ def test_bench_two_ranks_at_the_stated_per_gpu_size(kind):
     extra = [] if kind == "resnet_b64" else ["--model", "ecapa", "--augment"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--plain-timing", "--no-roofline", "--no-extra-configs"] + extra
+           "--warmup", "1", "--full", "--plain-timing", "--no-roofline", "--no-extra-configs"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _bench_line(r, out_json)

@@ -10,5 +10,5 @@ for V in "" $TAG "" $TAG; do
 done
 for V in "" $TAG "" $TAG; do
   if [ -z "$V" ]; then unset AIR_HIP_LIB; echo "== product"; else export AIR_HIP_LIB=$L/libair_hip.$V.so; echo "== $V"; fi
-  python bench.py --model ecapa --no-cpu-baseline --no-pmc --no-roofline --no-extra-configs --steps 50 2>/dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('timing',{}).get('windows_ms_per_step'))"
+  python bench.py --full --model ecapa --no-cpu-baseline --no-pmc --no-roofline --no-extra-configs --steps 50 2>/dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read())['windowed']; print(d['value'], d['ms_per_step'], d['timing']['windows_ms_per_step'])"
 done

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 export PYTHONPATH=$GRAFT_REPO_ROOT AIR_DIST_BACKEND=gloo
 run() {  # name, env...
   name=$1; shift
-  env "$@" AIR_BENCH_JSON_OUT=$OUT/n2_$name.json timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 500)) bench.py --gpus 2 --steps 10 --warmup 3 --plain-timing --no-roofline --no-extra-configs > $OUT/n2_$name.out 2> $OUT/n2_$name.err
+  env "$@" AIR_BENCH_JSON_OUT=$OUT/n2_$name.json timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 500)) bench.py --gpus 2 --steps 10 --warmup 3 --full --plain-timing --no-roofline --no-extra-configs > $OUT/n2_$name.out 2> $OUT/n2_$name.err
   python - <<P
 import json
 d=json.load(open("$OUT/n2_$name.json"))

@@ -28,6 +28,7 @@ class ParamArena:
             self.entries.append((n, p, off, cnt))
             off += (cnt + 3) // 4 * 4  # keep every view 16-byte aligned
         self.total = off
+        self.offsets = {n: o for n, _, o, _ in self.entries}
         self.head_total = 0
         for n, p, o, c in self.entries:
             if n not in tail_names:

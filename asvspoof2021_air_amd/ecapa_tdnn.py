@@ -34,6 +34,7 @@ import torch.nn as nn
 from . import _hip, ops
 from . import ops_h as oh
 from .arena import ParamArena
+from .schedule import BackwardSchedule
 
 
 class SEModule(nn.Module):
@@ -168,6 +169,8 @@ class _EcapaFn(torch.autograd.Function):
 
 
 class Res2Net2(nn.Module):
+    TAIL = ("fc7.weight", "fc7.bias", "bn7.weight", "bn7.bias")  # no gradient under ang_iso: last in the arena
+
     def __init__(self, block, C, model_scale, nOut, n_mels, encoder_type="ECA", context=True,
                  summed=False, out_bn=True, **kwargs):
         self.context = context
@@ -211,8 +214,10 @@ class Res2Net2(nn.Module):
         self.compute_dtype = "fp32"
         self._bucketer = None  # dist.GradBucketer when the all-reduce is overlapped with backward
         # weight gradients on a side HIP stream (they feed nothing until the optimiser): the MFMA-bound GEMMs and the
-        # small K = 3 kernels overlap the HBM-bound BatchNorm / pooling backward passes of the main stream
+        # small K = 3 kernels overlap the HBM-bound BatchNorm / pooling backward passes of the main stream.  A captured
+        # hipGraph keeps them on the main stream: its fork / join pairs replay slower (profiles/README.md).
         self.overlap_wgrad = os.environ.get("AIR_OVERLAP_WGRAD", "1") == "1"
+        self._side_stream = None
         self.fuse_tap_stats = os.environ.get("AIR_TAP_STATS", "1") == "1"  # Res2 branch statistics from the conv epilogue
         self.fuse_pw_stats = os.environ.get("AIR_PW_STATS", "1") == "1"    # K = 1 convs: statistics from the GEMM epilogue
         # (round 6) Res2 chain: the elementwise pass in front of a branch conv is that conv's prologue (bf16-resident path)
@@ -221,14 +226,6 @@ class Res2Net2(nn.Module):
         # time: the conv's fixed ~8 us per launch hides nothing of the extra streams), backward 16.56 k (-1.3 %: the
         # fused launch is 29.9 us where conv 14.8 + apply 9.4 were 24.2) - so forward on, backward off
         self.fuse_tap_prologue = int(os.environ.get("AIR_TAP_PROLOGUE", "1"))
-        self._side_stream = None
-        # Under hipGraph capture (train.Trainer.enable_graph) a fork per weight gradient makes a graph with ~14 cross-stream
-        # edges, which ROCm replays slower than one chain (round 4).  "batched" (experiment, AIR_WGRAD_BATCHED=1): the
-        # bf16-resident backward queues its weight-gradient launches and hands them to the side stream at FOUR points
-        # only - in front of each block's Res2 chain (21 short dependent launches that leave most of the chip idle) and
-        # at the end: 4 forks and 1 join.  Measured (round 5): still 5 ms of host time per replay and a slower step than
-        # one chain; left off.
-        self.wgrad_batched = False
 
     def enable_ddp_overlap(self, bucket_bytes=8 << 20):
         """Launch the gradient all-reduce from inside backward (one process per GPU, world size > 1):
@@ -267,8 +264,7 @@ class Res2Net2(nn.Module):
     def arena(self):
         dev = self.conv1.weight.device
         if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()),
-                                     tail_names=("fc7.weight", "fc7.bias", "bn7.weight", "bn7.bias"))
+            self._arena = ParamArena(list(self.named_parameters()), tail_names=self.TAIL)
         if not self._arena.bound() or self._arena.device != dev:
             self._arena.bind(dev)
         return self._arena
@@ -510,41 +506,15 @@ class Res2Net2(nn.Module):
         if S.get("resident"):
             return self._backward_h(S, dfeat, dout)
         arena = self.arena()
-        G = arena.grad_views()
-        # gradient accumulation (a second backward without zero_grad): p.grad already IS the arena view, so
-        # autograd's "p.grad += returned view" would double the NEW gradient instead of adding the old one.
-        # Keep the old sums aside, fold them back in at the end and return None for the aliased entries
-        # (same protocol as ResNet._backward_impl).
-        accumulating = any(p.grad is not None and p.grad.data_ptr() == G[n].data_ptr()
-                           for n, p, _, _ in arena.entries)
-        old = arena.grad.clone() if accumulating else None
+        # weight gradients on the side stream (schedule.py; see __init__), each bf16 operand copy they read in its own
+        # buffer; an accumulating pass runs as one chain
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=False)
+        G, on_side = sch.G, sch.on_side
         det = lambda p: p.detach()
         bf = S.get("bf16c", self.compute_dtype == "bf16c")
         B, _, T = S["x"].shape
         C = self.C
-        tail = ("fc7.weight", "fc7.bias", "bn7.weight", "bn7.bias")
         have_tail = dout is not None
-        # Weight gradients on the side stream (see __init__).  Ordering: a weight gradient starts after the event that
-        # marks its operands ready; tensors it reads are kept alive until the join (the caching allocator would hand
-        # their memory back to the main stream); every bf16 operand copy has its own buffer; the main stream joins
-        # the side stream before the gradients are used.
-        main = torch.cuda.current_stream()
-        use_side = self.overlap_wgrad and not accumulating
-        if use_side and self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(device=main.device)
-        side = self._side_stream if use_side else main
-        keep = []
-
-        def on_side(fn, *reads):
-            if not use_side:
-                fn()
-                return
-            keep.extend(reads)
-            ready = torch.cuda.Event()
-            ready.record(main)
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                fn()
         if dfeat is None:
             dfeat = torch.zeros_like(S["feat"])
         dfeat = dfeat.contiguous()
@@ -633,25 +603,7 @@ class Res2Net2(nn.Module):
                              dy_bf=dx4_bf)
 
         on_side(layer4_wgrad, dx4)
-        # data parallel: everything from layer4.weight to the end of the gradient arena is final
-        bucketer = None if accumulating else getattr(self, "_bucketer", None)
-        offsets = {n: o for n, _, o, _ in arena.entries}
-
-        def grads_final_from(first_param):
-            cut = getattr(self, "_segment_cut", None)
-            if cut is not None:  # train.Trainer's segmented hipGraph capture: a segment may end here
-                cut(offsets[first_param])
-            if bucketer is not None:
-                evs = [torch.cuda.Event()]
-                evs[0].record(main)
-                if use_side:
-                    evs.append(torch.cuda.Event())
-                    evs[1].record(side)
-                bucketer.ready(offsets[first_param], evs)
-
-        if bucketer is not None:
-            bucketer.reset(arena.grad, arena.head_total)
-        grads_final_from("layer4.weight")
+        sch.grads_final_from("layer4.weight")  # everything from layer4.weight to the end of the gradient arena
         # layer4's data gradient reads d(x4)'s bf16 copy (written by the context-statistics backward) K-major
         dcat123 = ops.conv1d_pointwise_kmajor(dx4_bf, det(self.layer4.weight), T, dgrad=True) if dx4_bf is not None else None
         if dcat123 is None:
@@ -677,7 +629,7 @@ class Res2Net2(nn.Module):
                                     on_side=on_side)
             if self.summed:
                 dsum = dnext if dsum is None else ops.add_(dsum, dnext)
-            grads_final_from("layer%d.conv1.weight" % (k + 1))
+            sch.grads_final_from("layer%d.conv1.weight" % (k + 1))
         if self.summed:
             dnext = dsum  # d(h) = d(input of block 1) + d(input of block 2) + d(input of block 3)
         st0 = S["st0"]
@@ -685,18 +637,7 @@ class Res2Net2(nn.Module):
                                relu_in=True, dx=dnext, dgamma=G["bn1.weight"], dbeta=G["bn1.bias"],
                                dbias=G["conv1.bias"])
         ops.conv1d_wgrad(S["x"], dc0, self.conv1.weight.shape, 1, 2, out=G["conv1.weight"])
-        if use_side:
-            main.wait_stream(side)  # join: every weight gradient is in the arena
-        del keep[:]
-        arena.tail_has_grad = have_tail
-        if accumulating:
-            if not have_tail:  # the tail got no new gradient: its old sums must survive the add below unchanged
-                arena.grad[arena.head_total:].zero_()
-            ops.add_(arena.grad, old)
-            arena.tail_has_grad = True  # old tail sums may be live; the optimiser covers the whole arena
-            return [None if (p.grad is not None and p.grad.data_ptr() == G[n].data_ptr())
-                    else (G[n] if (have_tail or n not in tail) else None) for n, p, _, _ in arena.entries]
-        return [G[n] if (have_tail or n not in tail) else None for n, _, _, _ in arena.entries]
+        return sch.finish(lambda n: have_tail or n not in self.TAIL, have_tail, keep_old_tail=True)
 
     # =================================================================== bf16-resident path (compute_dtype "bf16")
     def _conv1_rows(self):
@@ -851,9 +792,8 @@ class Res2Net2(nn.Module):
         ops.bn_flush()
         return feat, out, S
 
-    def _block_bwd_h(self, S, dout, T, G, pre, add2, on_side, flush_side=None):
-        """dout: gradient w.r.t. the block output (resident rows or a channel slice).  Returns d(inp) + dout + add2.
-        flush_side (batched weight gradients): called in front of the Res2 chain - what has been queued runs beside it."""
+    def _block_bwd_h(self, S, dout, T, G, pre, add2, on_side):
+        """dout: gradient w.r.t. the block output (resident rows or a channel slice).  Returns d(inp) + dout + add2."""
         blk = S["blk"]
         det = lambda p: p.detach()
         B, C, Tp = S["o3"].shape
@@ -877,8 +817,6 @@ class Res2Net2(nn.Module):
         din_next = sums_next = None
         dcs = [None] * nums
         fuse = getattr(self, "fuse_tap_stats", True)
-        if flush_side is not None:
-            flush_side()
         # (round 6) the BatchNorm-backward APPLY of branch i (h_bn_bwd_apply_kernel: 21 passes per step) is the prologue
         # of that branch's data-gradient conv, which reads r_i + the two gradient halves, computes dc_i while staging it
         # and writes it out for the weight gradient.  Its output (d t_i) goes into a second tensor, do1, slice by slice
@@ -932,48 +870,12 @@ class Res2Net2(nn.Module):
 
     def _backward_h(self, S, dfeat, dout):
         arena = self.arena()
-        G = arena.grad_views()
-        accumulating = any(p.grad is not None and p.grad.data_ptr() == G[n].data_ptr() for n, p, _, _ in arena.entries)
-        old = arena.grad.clone() if accumulating else None
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=False)
+        G, on_side = sch.G, sch.on_side
         det = lambda p: p.detach()
         B, _, T = S["x"].shape
         C = self.C
-        tail = ("fc7.weight", "fc7.bias", "bn7.weight", "bn7.bias")
         have_tail = dout is not None
-        main = torch.cuda.current_stream()
-        use_side = self.overlap_wgrad and not accumulating
-        if use_side and self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(device=main.device)
-        side = self._side_stream if use_side else main
-        batched = use_side and self.wgrad_batched
-        keep, pending = [], []
-
-        def on_side(fn, *reads):
-            if not use_side:
-                fn()
-                return
-            keep.extend(reads)
-            if batched:
-                pending.append(fn)
-                return
-            ready = torch.cuda.Event()
-            ready.record(main)
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                fn()
-
-        def flush_side():
-            """batched mode: everything queued so far goes to the side stream behind ONE event of the main stream"""
-            if not pending:
-                return
-            ready = torch.cuda.Event()
-            ready.record(main)
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                for fn in pending:
-                    fn()
-            del pending[:]
-
         if dfeat is None:
             dfeat = torch.zeros_like(S["feat"])
         dfeat = dfeat.contiguous()
@@ -1019,25 +921,7 @@ class Res2Net2(nn.Module):
         oh.row_stats_bwd(x4, T, S["mean"], S["std"], dmean, dstd, dx4, accumulate=True, relu_mask=True, rowsum=rows)
         ops.sum_rows(rows, out=G["layer4.bias"])
         on_side(lambda: oh.conv_wgrad(S["cat123"], dx4, T, G["layer4.weight"]), dx4)
-        bucketer = None if accumulating else getattr(self, "_bucketer", None)
-        offsets = {n: o for n, _, o, _ in arena.entries}
-
-        def grads_final_from(first_param):
-            cut = getattr(self, "_segment_cut", None)
-            if cut is not None:  # train.Trainer's segmented hipGraph capture: a segment may end here
-                cut(offsets[first_param])
-            if bucketer is not None:
-                flush_side()
-                evs = [torch.cuda.Event()]
-                evs[0].record(main)
-                if use_side:
-                    evs.append(torch.cuda.Event())
-                    evs[1].record(side)
-                bucketer.ready(offsets[first_param], evs)
-
-        if bucketer is not None:
-            bucketer.reset(arena.grad, arena.head_total)
-        grads_final_from("layer4.weight")
+        sch.grads_final_from("layer4.weight")
         dcat123 = oh.conv_pointwise(dx4, det(self.layer4.weight), T, dgrad=True)
         dnext = None
         for k in (2, 1, 0):
@@ -1045,8 +929,8 @@ class Res2Net2(nn.Module):
             # already added this block's slice (add2); block 3 reads its slice in place
             dblk = dcat123[:, k * C:(k + 1) * C] if dnext is None else dnext
             add2 = dcat123[:, (k - 1) * C:k * C] if k > 0 else None
-            dnext = self._block_bwd_h(S["blocks"][k], dblk, T, G, "layer%d." % (k + 1), add2, on_side, flush_side)
-            grads_final_from("layer%d.conv1.weight" % (k + 1))
+            dnext = self._block_bwd_h(S["blocks"][k], dblk, T, G, "layer%d." % (k + 1), add2, on_side)
+            sch.grads_final_from("layer%d.conv1.weight" % (k + 1))
         st0 = S["st0"]
         dc0 = oh.bn_bwd(S["r0"], dnext, T, st0[0], st0[1], det(self.bn1.weight), G["bn1.weight"], G["bn1.bias"], dx=dnext,
                         dbias=G["conv1.bias"])
@@ -1057,16 +941,4 @@ class Res2Net2(nn.Module):
             ops.add_strided(G["conv1.weight"].view(C, 1, nk), dwm.view(C, 1, R0)[:, :, :nk])  # drop the zero columns
 
         on_side(conv1_wgrad, dc0)
-        flush_side()
-        if use_side:
-            main.wait_stream(side)
-        del keep[:]
-        arena.tail_has_grad = have_tail
-        if accumulating:
-            if not have_tail:
-                arena.grad[arena.head_total:].zero_()
-            ops.add_(arena.grad, old)
-            arena.tail_has_grad = True
-            return [None if (p.grad is not None and p.grad.data_ptr() == G[n].data_ptr())
-                    else (G[n] if (have_tail or n not in tail) else None) for n, p, _, _ in arena.entries]
-        return [G[n] if (have_tail or n not in tail) else None for n, _, _, _ in arena.entries]
+        return sch.finish(lambda n: have_tail or n not in self.TAIL, have_tail, keep_old_tail=True)

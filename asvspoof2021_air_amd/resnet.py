@@ -26,6 +26,7 @@ import torch.nn.init as init
 
 from . import _hip, ops
 from .arena import ParamArena
+from .schedule import BackwardSchedule, side_stream
 
 
 class SelfAttention(nn.Module):
@@ -327,9 +328,7 @@ class ResNet(nn.Module):
         # one chain (overlap_wgrad off: the hipGraph capture of train.Trainer): the transforms run on the main stream
         # in front of the first layer that needs them, still as one launch per 32
         one_chain = not self.overlap_wgrad
-        if not one_chain and self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(device=main.device)
-        side = main if one_chain else self._side_stream
+        side = main if one_chain else side_stream(self)
         if not one_chain:
             start = torch.cuda.Event()
             start.record(main)  # the optimiser step that produced these weights is in front of it
@@ -481,13 +480,10 @@ class ResNet(nn.Module):
     # ----------------------------------------------------------------- backward
     def _backward_impl(self, S, dfeat, dmu):
         arena = self.arena()
-        G = arena.grad_views()
+        # weight gradients on the side stream (schedule.py), an accumulating pass included
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=True)
+        G, main = sch.G, sch.main
         have = set()
-        # gradient accumulation (backward twice without zero_grad): p.grad already IS the arena
-        # view, so keep the old sums aside and fold them back in at the end
-        accumulating = any(p.grad is not None and p.grad.data_ptr() == G[n].data_ptr()
-                           for n, p, _, _ in arena.entries)
-        old = arena.grad.clone() if accumulating else None
 
         def gv(mod_name):
             have.add(mod_name)
@@ -510,67 +506,14 @@ class ResNet(nn.Module):
         da5, datt = ops.selfatt_pool_bwd(S["a5v"], self.attention.att_weights.detach(), S["noise"],
                                          S["alpha"], S["pooled"], dpooled)
         ops.sum_rows(datt, out=gv("attention.att_weights").view(-1))
-        # Weight gradients feed nothing until the optimiser, so they run on a SIDE stream: the
-        # MFMA-bound wgrad kernels overlap the HBM-bound BatchNorm-backward passes and the tails
-        # of the dgrad chain on the main stream.  Ordering: a wgrad starts after the event that
-        # marks its dy ready; an in-place update of a tensor a wgrad still reads waits for that
-        # wgrad's event; the main stream joins the side stream before the gradients are used.
-        main = torch.cuda.current_stream()
-        use_side = self.overlap_wgrad
-        if use_side and self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(device=main.device)
-        side = self._side_stream if use_side else main
-        keep = []  # tensors the side stream reads: keep them alive until the join
-
-        def on_side(fn, *reads):
-            """Run fn() on the side stream once everything enqueued on main so far is done.
-            Returns an event marking its completion."""
-            if not use_side:
-                fn()
-                return None
-            keep.extend(reads)
-            ready = torch.cuda.Event()
-            ready.record(main)
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                fn()
-                done = torch.cuda.Event()
-                done.record(side)
-            return done
-
-        def wait_for(ev):
-            if ev is not None:
-                main.wait_event(ev)
-
-        offsets = {n: o for n, _, o, _ in arena.entries}
-        bucketer = getattr(self, "_bucketer", None)
-        if accumulating:
-            bucketer = None
-        if bucketer is not None:
-            bucketer.reset(arena.grad, arena.head_total)
-
-        def grads_final_from(first_param):
-            """Everything that writes arena.grad[offset(first_param):] has been enqueued."""
-            cut = getattr(self, "_segment_cut", None)
-            if cut is not None:  # train.Trainer's segmented hipGraph capture: a segment may end here
-                cut(offsets[first_param])
-            if bucketer is None:
-                return
-            evs = [torch.cuda.Event()]
-            evs[0].record(main)
-            if use_side:
-                evs.append(torch.cuda.Event())
-                evs[1].record(side)
-            bucketer.ready(offsets[first_param], evs)
-
         c5, st5 = S["c5"], S["st5"]
         dc5, _, _ = ops.bn_bwd(c5, da5.view_as(c5), st5[0], st5[1], self.bn5.weight.detach(),
                                self.bn5.bias.detach(), relu=True,
                                dgamma=gv("bn5.weight"), dbeta=gv("bn5.bias"))
         l4 = S["l4"]
         g5 = gv("conv5.weight")
-        on_side(lambda: ops.conv2d_wgrad(l4, dc5, self.conv5.weight.shape, 1, (0, 1), out=g5), dc5)
-        grads_final_from("conv5.weight")
+        sch.on_side(lambda: ops.conv2d_wgrad(l4, dc5, self.conv5.weight.shape, 1, (0, 1), out=g5), dc5)
+        sch.grads_final_from("conv5.weight")
         fuse = self.fuse_bn_into_conv
         packs = S.get("packs") or {}
         if packs and S.get("pack_ev") is not None:
@@ -598,7 +541,7 @@ class ResNet(nn.Module):
                 if has_sc:
                     ops.conv2d_wgrad(actA, dcur, blk.shortcut[0].weight.shape, s, 0, out=gsc, **pA)
 
-            ev_dcur = on_side(wg_out, dcur)
+            ev_dcur = sch.on_side(wg_out, dcur, done=not has_sc)
             # d(relu(bn2(h))) from conv2's data gradient - whose epilogue also takes the two sums of bn2's backward
             # (round 4: ops returns None where the layer has no Winograd data gradient)
             bn_fuse = getattr(self, "fuse_bn_stats", True) and not fuse
@@ -608,8 +551,8 @@ class ResNet(nn.Module):
                                   blk.bn2.bias.detach(), relu=True, dx=d_actB, sums_in=smB,
                                   dgamma=gv(pre + "bn2.weight"), dbeta=gv(pre + "bn2.bias"))
             g1 = gv(pre + "conv1.weight")
-            on_side(lambda dh=dh, actA=actA, blk=blk, s=s, pA=pA, g1=g1:
-                    ops.conv2d_wgrad(actA, dh, blk.conv1.weight.shape, s, 1, out=g1, **pA), dh)
+            sch.on_side(lambda dh=dh, actA=actA, blk=blk, s=s, pA=pA, g1=g1:
+                        ops.conv2d_wgrad(actA, dh, blk.conv1.weight.shape, s, 1, out=g1, **pA), dh)
             # (with a 1x1 shortcut d_actA gets a second term below: the sums would be of a partial gradient)
             bnA = (xin, stA[0], stA[1], blk.bn1.weight.detach(), blk.bn1.bias.detach()) if bn_fuse and not has_sc else None
             pair = has_sc and s == 2 and ops.conv2d_dgrad_s2_pair_ok(blk.conv1.weight.shape, xin.shape)
@@ -628,24 +571,16 @@ class ResNet(nn.Module):
             else:
                 # identity shortcut: d(block input) = bn1-backward(d_actA) + dcur, joined in place
                 # (dcur is still being read by this block's conv2 wgrad on the side stream)
-                wait_for(ev_dcur)
+                if ev_dcur is not None:
+                    main.wait_event(ev_dcur)
                 dcur, _, _ = ops.bn_bwd(xin, d_actA, stA[0], stA[1], blk.bn1.weight.detach(),
                                         blk.bn1.bias.detach(), relu=True, dx=dcur, accumulate=True, sums_in=smA,
                                         dgamma=gv(pre + "bn1.weight"), dbeta=gv(pre + "bn1.bias"))
-            grads_final_from(pre + "bn1.weight")  # the block's first parameter in arena order
+            sch.grads_final_from(pre + "bn1.weight")  # the block's first parameter in arena order
         c1, st1 = S["c1"], S["st1"]
         dc1, _, _ = ops.bn_bwd(c1, dcur, st1[0], st1[1], self.bn1.weight.detach(),
                                self.bn1.bias.detach(), relu=True, dx=dcur,
                                dgamma=gv("bn1.weight"), dbeta=gv("bn1.bias"))
         gc1 = gv("conv1.weight")
-        ev = on_side(lambda: ops.conv2d_wgrad(S["x"], dc1, self.conv1.weight.shape, (3, 1), (1, 1), out=gc1),
-                     dc1)
-        if use_side:
-            main.wait_stream(side)  # join: every weight gradient is in the arena
-        keep.clear()
-        arena.tail_has_grad = "fc_mu.weight" in have
-        if accumulating:
-            ops.add_(arena.grad, old)
-            return [None if (p.grad is not None and p.grad.data_ptr() == G[n].data_ptr())
-                    else (G[n] if n in have else None) for n, p, _, _ in arena.entries]
-        return [G[n] if n in have else None for n, _, _, _ in arena.entries]
+        sch.on_side(lambda: ops.conv2d_wgrad(S["x"], dc1, self.conv1.weight.shape, (3, 1), (1, 1), out=gc1), dc1)
+        return sch.finish(have.__contains__, "fc_mu.weight" in have)

@@ -235,31 +235,12 @@ class Trainer:
         self.graph_segments = bool(segments) and self.use_graph
         self._drop_graph()
         if self.use_graph:
-            # Round 4, root cause of "replay slower than eager" (tools/exp_ecapa_graph.sh): with the weight gradients
-            # on the side stream the captured graph has a fork / join pair per layer, and ROCm replays such a graph
-            # through several internal streams with a signal per edge - hipGraphLaunch itself took 5.4 ms of host time
-            # per replay and the step 8.41 ms against eager's 8.16.  Captured as ONE chain (no side stream) the replay
-            # costs 0.22 ms of host time and the step 8.08 ms (6.19 ms at T = 401, eager 6.24).
-            # Round 5 re-test with FOUR forks and one join (Res2Net2.wgrad_batched: the weight gradients queued and handed
-            # to the side stream in front of each block's Res2 chain; AIR_WGRAD_BATCHED=1): hipGraphLaunch 5.1 ms of host
-            # time again, step 7.58 ms against 7.40 as one chain (5.60 / 5.42 at T = 401) - ANY fork makes the replay
-            # multi-stream.  Off by default.
+            # captured as ONE chain: a graph with the side stream's fork / join pairs replays slower (profiles/r06_launch_modes.md)
             if self._overlap_saved is None:  # (a second enable_graph() must not save the already-forced False)
-                self._overlap_saved = (getattr(self.model, "overlap_wgrad", None), getattr(self.model, "_bucketer", None))
-            batched = (isinstance(self.model, Res2Net2) and getattr(self.model, "compute_dtype", "fp32") == "bf16"
-                       and os.environ.get("AIR_WGRAD_BATCHED", "0") == "1")
-            # (A/B, AIR_GRAPH_FORKS=1: keep the side stream under capture - a graph with a fork / join pair per weight gradient)
-            self.model.overlap_wgrad = batched or os.environ.get("AIR_GRAPH_FORKS", "0") == "1"
-            if isinstance(self.model, Res2Net2):
-                self.model.wgrad_batched = batched
-            if hasattr(self.model, "_bucketer"):
-                self.model._bucketer = None
+                self._overlap_saved = (self.model.overlap_wgrad, self.model._bucketer)
+            self.model.overlap_wgrad, self.model._bucketer = False, None
         elif self._overlap_saved is not None:
-            self.model.overlap_wgrad, bucketer = self._overlap_saved
-            if hasattr(self.model, "wgrad_batched"):
-                self.model.wgrad_batched = False
-            if hasattr(self.model, "_bucketer"):
-                self.model._bucketer = bucketer
+            self.model.overlap_wgrad, self.model._bucketer = self._overlap_saved
             self._overlap_saved = None
         return self
 
@@ -309,37 +290,31 @@ class Trainer:
                 p.grad = gr
         g["pcm"].copy_(pcm, non_blocking=True)
         g["labels"].copy_(labels, non_blocking=True)
+        # graph k's replay, then (world > 1, segments) the all-reduce of the arena slice it completed - launched on the
+        # communication stream behind an event, so that the next replay is enqueued right away
+        bucketer = None
+        if self.world > 1 and g["segments"]:
+            if self._seg_bucketer is None:
+                self._seg_bucketer = air_dist.GradBucketer(self.segment_bytes)
+            bucketer = self._seg_bucketer
+            arena = self.model.arena()
+            bucketer.reset(arena.grad, arena.head_total)
+        main = torch.cuda.current_stream()
+        for graph, lo in g["graphs"]:
+            graph.replay()
+            if bucketer is not None and lo is not None:
+                ev = torch.cuda.Event()
+                ev.record(main)
+                bucketer.lo, bucketer.events = lo, [ev]
+                bucketer.flush()
         scale = 1.0
-        if g.get("segments") is None:
-            g["graph"].replay()
-            if self.world > 1:  # the one exchange of the step, behind the replay (no bucketer while the graph is on)
+        if self.world > 1:  # the remaining exchange of the step, behind the replay (no in-backward bucketer while the graph is on)
+            self.model._bucketer = bucketer  # (allreduce_grads waits for what was sent and reduces the remaining head)
+            try:
                 air_dist.allreduce_grads(self.model, self.loss)
-                scale = 1.0 / self.world
-        else:
-            # segment k's replay, then (world > 1) the all-reduce of the arena slice it completed - launched on the
-            # communication stream behind an event, so that the next replay is enqueued right away
-            bucketer = None
-            if self.world > 1:
-                if self._seg_bucketer is None:
-                    self._seg_bucketer = air_dist.GradBucketer(self.segment_bytes)
-                bucketer = self._seg_bucketer
-                arena = self.model.arena()
-                bucketer.reset(arena.grad, arena.head_total)
-            main = torch.cuda.current_stream()
-            for graph, lo in g["segments"]:
-                graph.replay()
-                if bucketer is not None and lo is not None:
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    bucketer.lo, bucketer.events = lo, [ev]
-                    bucketer.flush()
-            if self.world > 1:
-                self.model._bucketer = bucketer  # (allreduce_grads waits for what was sent and reduces the remaining head)
-                try:
-                    air_dist.allreduce_grads(self.model, self.loss)
-                finally:
-                    self.model._bucketer = None
-                scale = 1.0 / self.world
+            finally:
+                self.model._bucketer = None
+            scale = 1.0 / self.world
         self.feat_optimizer.step(grad_scale=scale)
         self.loss_optimizer.step(grad_scale=scale)
         return g["loss"].detach().clone(), g["neg"].clone()
@@ -385,8 +360,9 @@ class Trainer:
         pairs += [(p, p.grad) for p in self.loss.parameters() if p.grad is not None]
         return loss, neg, pairs
 
-    def _capture_segments(self, key, pcm, labels):
-        """The step as several hipGraphs sharing one memory pool, cut at backward's bucket boundaries (enable_graph)."""
+    def _capture(self, key, pcm, labels):
+        """The step recorded through _fwd_bwd_direct on a capture stream: one hipGraph, or (graph_segments) several sharing
+        one memory pool, cut at backward's bucket boundaries (enable_graph)."""
         from . import ops
         self.model.train()
         s_pcm, s_labels = pcm.detach().clone(), labels.detach().clone()
@@ -395,7 +371,7 @@ class Trainer:
         arena = self.model.arena()
         pool = torch.cuda.graph_pool_handle()
         state = {"g": None, "hi": arena.head_total}
-        segments = []
+        graphs = []  # (graph, lo): replaying it completes arena.grad[lo:hi]; lo None for the last one
 
         # world > 1: other threads of the process (the process group's watchdog polling its events) make runtime calls
         # while this thread captures; "thread_local" checks only the capturing thread's calls (the default, "global",
@@ -411,7 +387,7 @@ class Trainer:
             if lo >= state["hi"] or (state["hi"] - lo) * 4 < self.segment_bytes:
                 return
             state["g"].capture_end()
-            segments.append((state["g"], lo))
+            graphs.append((state["g"], lo))
             state["hi"] = lo
             begin()
 
@@ -421,7 +397,7 @@ class Trainer:
         torch.cuda.empty_cache()
         cap = torch.cuda.Stream(device=self.device)
         cap.wait_stream(torch.cuda.current_stream())
-        self.model._segment_cut = cut
+        self.model._segment_cut = cut if self.graph_segments else None  # (no cut: one graph)
         try:
             with torch.cuda.stream(cap):
                 begin()
@@ -434,7 +410,7 @@ class Trainer:
                         pass
                     raise
                 state["g"].capture_end()
-                segments.append((state["g"], None))  # the rest of the arena goes with the final all-reduce
+                graphs.append((state["g"], None))  # the rest of the arena goes with the final all-reduce
         finally:
             self.model._segment_cut = None
         torch.cuda.current_stream().wait_stream(cap)
@@ -442,34 +418,10 @@ class Trainer:
         if not getattr(self, "_pin_finalizer", None):
             import weakref
             self._pin_finalizer = weakref.finalize(self, ops.unpin_workspaces, id(self))
-        self._graph = dict(key=key, graph=None, segments=segments, pool=pool, pcm=s_pcm, labels=s_labels, loss=loss, neg=neg,
-                           grads=grads, ws_gen=ops.workspace_generation())
-        return self._graph
-
-    def _capture(self, key, pcm, labels):
-        from . import ops
-        if self.graph_segments:
-            return self._capture_segments(key, pcm, labels)
-        self.model.train()
-        s_pcm, s_labels = pcm.detach().clone(), labels.detach().clone()
-        self.feat_optimizer.zero_grad()
-        self.loss_optimizer.zero_grad()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local" if self.world > 1 else "global"):
-            feats, _ = self.model(self.features(s_pcm, None))
-            loss, neg = self.loss(feats, s_labels)
-            (loss if self.weight_loss == 1.0 else loss * self.weight_loss).backward()
         # p.grad now ARE the tensors the captured kernels write (no zero_grad between replays - every gradient is
-        # overwritten, none accumulated); kept here so _graphed_step can restore them after eager interludes
-        grads = [(p, p.grad) for p in list(self.model.parameters()) + list(self.loss.parameters())
-                 if p.grad is not None]
-        ops.pin_workspaces(id(self))
-        if not getattr(self, "_pin_finalizer", None):
-            import weakref
-            self._pin_finalizer = weakref.finalize(self, ops.unpin_workspaces, id(self))
-        self._graph = dict(key=key, graph=graph, pcm=s_pcm, labels=s_labels, loss=loss, neg=neg, grads=grads,
-                           ws_gen=ops.workspace_generation())
+        # overwritten, none accumulated); kept in "grads" so _graphed_step can restore them after eager interludes
+        self._graph = dict(key=key, graphs=graphs, segments=graphs if self.graph_segments else None, pool=pool, pcm=s_pcm,
+                           labels=s_labels, loss=loss, neg=neg, grads=grads, ws_gen=ops.workspace_generation())
         return self._graph
 
     @torch.no_grad()

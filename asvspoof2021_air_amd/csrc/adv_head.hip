@@ -22,9 +22,10 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2])
   k[1] += 0xBB67AE85u;
 }
 
-// nn.Dropout(p) keep-mask, already scaled: keep = (u >= p) / (1 - p), u ~ U[0,1) from Philox4x32-10
-__global__ __launch_bounds__(NT) void dropout_mask_kernel(float* __restrict__ keep, size_t n, float p,
-                                                          uint64_t seed, uint64_t offset) {
+// nn.Dropout(p) keep-mask, already scaled: keep = (u >= p) / (1 - p), u ~ U[0,1) from Philox4x32-10.  One body for
+// the host-offset draw and the device-counter draw (air_dropout_mask_ctr), so that the two cannot drift apart.
+__device__ __forceinline__ void dropout_body(float* __restrict__ keep, size_t n, float p, uint64_t seed,
+                                             uint64_t offset) {
   const size_t quad = (size_t)blockIdx.x * NT + threadIdx.x;
   if (quad * 4 >= n) return;
   const uint64_t ctr = offset + quad;
@@ -36,6 +37,20 @@ __global__ __launch_bounds__(NT) void dropout_mask_kernel(float* __restrict__ ke
   for (int j = 0; j < 4; ++j)
     if (quad * 4 + j < n) keep[quad * 4 + j] = ((float)c[j] * 2.3283064365386963e-10f >= p) ? scale : 0.0f;
 }
+
+__global__ __launch_bounds__(NT) void dropout_mask_kernel(float* __restrict__ keep, size_t n, float p,
+                                                          uint64_t seed, uint64_t offset) {
+  dropout_body(keep, n, p, seed, offset);
+}
+
+// The same draw with the Philox offset read from device memory, and the 1-thread kernel that advances it behind the
+// draw (a captured hipGraph would freeze a host-side offset)
+__global__ __launch_bounds__(NT) void dropout_mask_ctr_kernel(float* __restrict__ keep, size_t n, float p,
+                                                              uint64_t seed,
+                                                              const unsigned long long* __restrict__ counter) {
+  dropout_body(keep, n, p, seed, (uint64_t)*counter);
+}
+__global__ void dropout_ctr_add_kernel(unsigned long long* counter, unsigned long long inc) { *counter += inc; }
 
 // y = relu(x * keep)   (Dropout -> ReLU, model.py:1013-1014; keep NULL in eval mode)
 __global__ __launch_bounds__(NT) void mask_relu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ keep,
@@ -116,6 +131,19 @@ int air_dropout_mask(float* keep, size_t n, float p, uint64_t seed, uint64_t off
   if (!keep || n == 0 || !(p >= 0.0f) || !(p < 1.0f)) return AIR_EINVAL;
   hipLaunchKernelGGL(dropout_mask_kernel, dim3(nblk((n + 3) / 4)), dim3(NT), 0, air_stream(stream), keep, n, p, seed,
                      offset);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_dropout_mask_ctr(float* keep, size_t n, float p, uint64_t seed, uint64_t* counter, air_stream_t stream) {
+  if (!keep || n == 0 || !(p >= 0.0f) || !(p < 1.0f) || !counter || (reinterpret_cast<size_t>(counter) & 7))
+    return AIR_EINVAL;
+  const size_t quads = (n + 3) / 4;
+  hipLaunchKernelGGL(dropout_mask_ctr_kernel, dim3(nblk(quads)), dim3(NT), 0, air_stream(stream), keep, n, p, seed,
+                     reinterpret_cast<const unsigned long long*>(counter));
+  AIR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(dropout_ctr_add_kernel, dim3(1), dim3(1), 0, air_stream(stream),
+                     reinterpret_cast<unsigned long long*>(counter), (unsigned long long)quads);
   AIR_CHECK_LAUNCH();
   return AIR_OK;
 }

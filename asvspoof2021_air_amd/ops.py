@@ -466,6 +466,87 @@ def randn_ctr(shape, device, seed, counter, scale=1.0):
     return out
 
 
+# ------------------------------------------------------------------ LCNN (lcnn.py)
+def lcnn_conv1_fwd(x, w, bias):
+    """conv1 of model.py:528-530 fused: (pooled MFM output (B, 32, H/2, W/2), route bytes of the same shape)."""
+    B, _, H, W = x.shape
+    y = torch.empty((B, 32, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    route = torch.empty(y.shape, device=x.device, dtype=torch.uint8)
+    _hip.check(_hip.lib().air_lcnn_conv1_fwd(dptr(x), dptr(w), dptr(bias), ci(B), ci(H), ci(W), dptr(y),
+                                             dptr(route, torch.uint8), stream()), "air_lcnn_conv1_fwd")
+    return y, route
+
+
+def lcnn_conv1_wgrad(x, dy, route, dw, db):
+    B, _, H, W = x.shape
+    n = int(_hip.lib().air_lcnn_conv1_wgrad_ws_bytes())
+    ws = workspace(n, x.device)
+    _hip.check(_hip.lib().air_lcnn_conv1_wgrad(dptr(x), dptr(dy), dptr(route, torch.uint8), ci(B), ci(H), ci(W),
+                                               dptr(dw), dptr(db), dptr(ws, torch.uint8), csz(n), stream()),
+               "air_lcnn_conv1_wgrad")
+    return dw, db
+
+
+def mfm_pool_fwd(x, C=None, bias=None, pool=False):
+    """MaxFeatureMap2D over channels [0, C) of x (B, Ctot, H, W) (+ bias), then an optional 2x2 floor-mode max-pool.
+    Returns (y (B, C/2, Ho, Wo), route bytes)."""
+    B, Ctot, H, W = x.shape
+    C = Ctot if C is None else C
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    y = torch.empty((B, C // 2, Ho, Wo), device=x.device, dtype=torch.float32)
+    route = torch.empty(y.shape, device=x.device, dtype=torch.uint8)
+    _hip.check(_hip.lib().air_mfm_pool_fwd(dptr(x), dptr(bias, allow_none=True), ci(B), ci(Ctot), ci(C), ci(H), ci(W),
+                                           ci(1 if pool else 0), dptr(y), dptr(route, torch.uint8), stream()),
+               "air_mfm_pool_fwd")
+    return y, route
+
+
+def mfm_pool_bwd(dy, route, x_shape, C=None, pool=False, out=None):
+    """Gradient with respect to mfm_pool_fwd's x: dy where the element won, zero elsewhere."""
+    B, Ctot, H, W = x_shape
+    C = Ctot if C is None else C
+    dx = out if out is not None else torch.empty(tuple(x_shape), device=dy.device, dtype=torch.float32)
+    _hip.check(_hip.lib().air_mfm_pool_bwd(dptr(dy), dptr(route, torch.uint8), ci(B), ci(Ctot), ci(C), ci(H), ci(W),
+                                           ci(1 if pool else 0), dptr(dx), stream()), "air_mfm_pool_bwd")
+    return dx
+
+
+def mfm_bias_grad(dy, route, out=None):
+    """Bias gradient of the convolution in front of an MFM: (C,) from dy (B, C/2, ...) and its route bytes."""
+    B, C2 = dy.shape[0], dy.shape[1]
+    S = dy.numel() // (B * C2)
+    db = out if out is not None else torch.empty(2 * C2, device=dy.device, dtype=torch.float32)
+    n = int(_hip.lib().air_mfm_bias_grad_ws_bytes(ci(2 * C2)))
+    ws = workspace(n, dy.device)
+    _hip.check(_hip.lib().air_mfm_bias_grad(dptr(dy), dptr(route, torch.uint8), ci(B), ci(2 * C2), ci(S), dptr(db),
+                                            dptr(ws, torch.uint8), csz(n), stream()), "air_mfm_bias_grad")
+    return db
+
+
+def copy_pad(dst, src):
+    """dst[:n] = src[:n] (n = the smaller size), zeros behind src in dst."""
+    _hip.check(_hip.lib().air_copy_pad(dptr(dst), csz(dst.numel()), dptr(src), csz(src.numel()), stream()),
+               "air_copy_pad")
+    return dst
+
+
+def mul(a, b, out=None):
+    y = out if out is not None else torch.empty_like(a)
+    _hip.check(_hip.lib().air_mul(dptr(a), dptr(b), csz(a.numel()), dptr(y), stream()), "air_mul")
+    return y
+
+
+def dropout_mask_ctr(shape, p, seed, counter, device):
+    """nn.Dropout(p)'s scaled keep-mask from Philox4x32-10 with the offset in ``counter`` (1-element int64 GPU
+    tensor, advanced on the stream): capturable, and eager calls and replays walk one sequence."""
+    if counter.dtype != torch.int64 or not counter.is_cuda or counter.numel() != 1:
+        raise _hip.AirError("dropout_mask_ctr: counter must be a 1-element int64 GPU tensor")
+    keep = torch.empty(shape, device=device, dtype=torch.float32)
+    _hip.check(_hip.lib().air_dropout_mask_ctr(dptr(keep), csz(keep.numel()), cf(p), ctypes.c_uint64(seed),
+                                               dptr(counter, torch.int64), stream()), "air_dropout_mask_ctr")
+    return keep
+
+
 # ------------------------------------------------------------------ ECAPA (B, C, T) ops
 def vptr(t):
     """(pointer, batch stride) of a (B, C, T) tensor or channel-slice view whose (C, T)

@@ -227,8 +227,9 @@ class Trainer:
         step AND BASELINE configs[3]'s "all-reduce overlapped with backward".  Same kernels in the same order as the
         one-chain capture and as the eager step: bit-identical (tests/test_dist_gpu.py)."""
         from .ecapa_tdnn import Res2Net2
+        from .lcnn import LCNN
         from .resnet import ResNet
-        self.use_graph = bool(on) and isinstance(self.model, (Res2Net2, ResNet))
+        self.use_graph = bool(on) and isinstance(self.model, (Res2Net2, ResNet, LCNN))
         if segments is None:
             env = os.environ.get("AIR_GRAPH_SEGMENTS", "")
             segments = (env == "1") if env in ("0", "1") else self.world > 1

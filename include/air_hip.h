@@ -710,6 +710,45 @@ int air_h_copy(const unsigned short* x, size_t x_bs, int B, int C, int Tp, unsig
 int air_h_unfold(const float* x, size_t x_bs, int B, int Cin, int T, int Tp, int K, int dil, int pad, int rows,
                  unsigned short* y, size_t y_bs, air_stream_t stream);
 
+/* ----------------------------------------------------------------- LCNN ---
+ * model.LCNN (model.py:511-610), the reference's default --model.  Its convolutions conv2 .. conv9 run on
+ * air_conv2d_fwd_pre / _dgrad_pre / _wgrad (bias-free; conv3 / conv4's 96 outputs on weights zero-padded to 128
+ * rows), its BatchNorm2d(affine=False) on the BatchNorm kernels with unit scale and zero shift, its Linear layers on
+ * air_linear_*.  The kernels below are the rest.  Route byte of every post-MFM (post-pool) element: bits 0-1 the
+ * winning 2x2 window position (dy * 2 + dx; 0 without pooling), bit 2 the Max-Feature-Map half (0: channel c, 1:
+ * channel c + C/2).  Ties go to the first candidate, as torch's max(dim) / max_pool2d send the gradient. */
+/* conv1 (model.py:528-530): Conv2d(1, 64, 5, pad 2) + bias -> MaxFeatureMap2D -> MaxPool2d(2, 2) in one pass.
+ * x (B, 1, H, W), w (64, 1, 5, 5), bias (64); y and route (B, 32, H/2, W/2).  The 64 x H x W map is never written. */
+int air_lcnn_conv1_fwd(const float* x, const float* w, const float* bias, int B, int H, int W, float* y,
+                       uint8_t* route, air_stream_t stream);
+/* conv1's weight (64, 25) and bias (64) gradients from the pooled gradient dy (B, 32, H/2, W/2) and the route bytes
+ * (no data gradient: the input is features).  Deterministic (fixed-order reduction). */
+size_t air_lcnn_conv1_wgrad_ws_bytes(void);
+int air_lcnn_conv1_wgrad(const float* x, const float* dy, const uint8_t* route, int B, int H, int W, float* dw,
+                         float* db, void* ws, size_t ws_bytes, air_stream_t stream);
+/* MaxFeatureMap2D (model.py:512-545) of x + bias over channels [0, C) of x (B, Ctot, H, W), then with pool != 0
+ * MaxPool2d(2, 2) (floor mode: an odd last row / column is dropped): y, route (B, C/2, Ho, Wo).  bias (C) may be
+ * NULL (the conv's bias folded in here: model.py:531-563 convs all have one). */
+int air_mfm_pool_fwd(const float* x, const float* bias, int B, int Ctot, int C, int H, int W, int pool, float* y,
+                     uint8_t* route, air_stream_t stream);
+/* The route backward: dx (B, Ctot, H, W) = dy where the element won its pair and window, 0 elsewhere (losers,
+ * dropped rows / columns, padded channels [C, Ctot)). */
+int air_mfm_pool_bwd(const float* dy, const uint8_t* route, int B, int Ctot, int C, int H, int W, int pool, float* dx,
+                     air_stream_t stream);
+/* The conv bias gradient behind an MFM: db[ch] (C) = sum of dy (B, C/2, S) over the positions channel ch won.
+ * Deterministic. */
+size_t air_mfm_bias_grad_ws_bytes(int C);
+int air_mfm_bias_grad(const float* dy, const uint8_t* route, int B, int C, int S, float* db, void* ws, size_t ws_bytes,
+                      air_stream_t stream);
+/* dst[i] = src[i] for i < min(n_dst, n_src), 0 beyond n_src: zero-padded weight rows and the gradient rows copied back. */
+int air_copy_pad(float* dst, size_t n_dst, const float* src, size_t n_src, air_stream_t stream);
+/* y = a * b elementwise: nn.Dropout(0.7) of model.py:601 forward and backward with the keep-mask. */
+int air_mul(const float* a, const float* b, size_t n, float* y, air_stream_t stream);
+/* air_dropout_mask with the Philox offset held in DEVICE memory (read, then advanced by ceil(n / 4) behind the
+ * draw), like air_randn_ctr: a captured hipGraph draws a fresh mask on every replay.  Same draw body as
+ * air_dropout_mask (adv_head.hip).  counter: 8-byte aligned. */
+int air_dropout_mask_ctr(float* keep, size_t n, float p, uint64_t seed, uint64_t* counter, air_stream_t stream);
+
 /* ----------------------------------------------------------- OC-Softmax ---
  * AngularIsoLoss.forward == OCSoftmax.forward (loss.py:73-97, :187-206).
  * x (B,D), center (1,D), labels (B,) int64.  loss: scalar; neg_scores (B,).

@@ -254,11 +254,13 @@ class Res2Net2(nn.Module):
         """The train-mode forward WITHOUT autograd: (feat, saved) - see ResNet.forward_saved."""
         x = x.float().contiguous()
         self.arena()
-        feat, _, saved = self._forward_impl(x, save=True)
+        feat, out, saved = self._forward_impl(x, save=True)
+        saved["logits"] = out  # the CE head's input (train.Trainer, add_loss=None)
         return feat, saved
 
-    def backward_saved(self, saved, dfeat):
-        return self._backward_impl(saved, dfeat, None)
+    def backward_saved(self, saved, dfeat, dout=None):
+        """dout: the gradient of saved["logits"] (the CE head through fc7 / bn7), or None."""
+        return self._backward_impl(saved, dfeat, dout)
 
     # ------------------------------------------------------------------ plumbing
     def arena(self):
@@ -515,9 +517,6 @@ class Res2Net2(nn.Module):
         B, _, T = S["x"].shape
         C = self.C
         have_tail = dout is not None
-        if dfeat is None:
-            dfeat = torch.zeros_like(S["feat"])
-        dfeat = dfeat.contiguous()
         if have_tail:  # CE branch through fc7/bn7 (dead under ang_iso, main_train.py:355 -> 376)
             do7 = dout.contiguous()
             if self.out_bn:
@@ -528,7 +527,10 @@ class Res2Net2(nn.Module):
                 do7 = do7.view(B, -1)
             dx7, _, _ = ops.linear_bwd(S["feat"], det(self.fc7.weight), do7, True, dw=G["fc7.weight"],
                                        db=G["fc7.bias"])
-            dfeat = ops.add_(dx7, dfeat)
+            dfeat = dx7 if dfeat is None else ops.add_(dx7, dfeat.contiguous())
+        if dfeat is None:
+            dfeat = torch.zeros_like(S["feat"])
+        dfeat = dfeat.contiguous()
         dp5, _, _ = ops.linear_bwd(S["p5"], det(self.fc6.weight), dfeat, True, dw=G["fc6.weight"],
                                    db=G["fc6.bias"])
         st5 = S["st5"]
@@ -876,9 +878,6 @@ class Res2Net2(nn.Module):
         B, _, T = S["x"].shape
         C = self.C
         have_tail = dout is not None
-        if dfeat is None:
-            dfeat = torch.zeros_like(S["feat"])
-        dfeat = dfeat.contiguous()
         if have_tail:  # CE branch through fc7/bn7 (dead under ang_iso, main_train.py:355 -> 376)
             do7 = dout.contiguous()
             if self.out_bn:
@@ -887,7 +886,10 @@ class Res2Net2(nn.Module):
                                        det(self.bn7.bias), dgamma=G["bn7.weight"], dbeta=G["bn7.bias"])
                 do7 = do7.view(B, -1)
             dx7, _, _ = ops.linear_bwd(S["feat"], det(self.fc7.weight), do7, True, dw=G["fc7.weight"], db=G["fc7.bias"])
-            dfeat = ops.add_(dx7, dfeat)
+            dfeat = dx7 if dfeat is None else ops.add_(dx7, dfeat.contiguous())
+        if dfeat is None:
+            dfeat = torch.zeros_like(S["feat"])
+        dfeat = dfeat.contiguous()
         dp5, _, _ = ops.linear_bwd(S["p5"], det(self.fc6.weight), dfeat, True, dw=G["fc6.weight"], db=G["fc6.bias"])
         st5 = S["st5"]
         dpooled, _, _ = ops.bn_bwd(S["pooled"].view(B, -1, 1), dp5.view(B, -1, 1), st5[0], st5[1], det(self.bn5.weight),

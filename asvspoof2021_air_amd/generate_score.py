@@ -2,7 +2,8 @@
 
 ``test_on_dataset`` keeps the reference's loop - eval-mode model, per-item ``lfcc.transpose(2, 3)``
 (``.squeeze(1)`` for ECAPA, :91-94), ``feats, outputs = model(lfcc)``, default score
-``-softmax(outputs)[:, 0]`` (:102), ``--loss ocsoftmax`` score from the loss module (:104-105) -
+``-softmax(outputs)[:, 0]`` (:102), ``--loss ocsoftmax`` / ``p2sgrad`` score = the loss module's second output
+(:104-105, :109-110), ``--loss amsoftmax`` score = ``softmax(logits)[:, 0]`` of the module's cosines (:106-108) -
 and the exact score-file text (:113-119): ``'%s %s %s\\n' % (name, -score, key)`` for the
 ASVspoof2019 tasks, ``'%s %s\\n'`` for the 2021 evaluation sets.  Differences, both
 arithmetic-neutral: any batch size (the reference uses 1; eval-mode BatchNorm makes utterances
@@ -39,11 +40,15 @@ def batch_scores(model, lfcc, loss_model=None, add_loss=None):
     feats, outputs = model(lfcc)
     if add_loss is None:
         return -ops.softmax_rows(outputs)[:, 0]  # :102
-    if add_loss == "ocsoftmax":
-        labels = torch.zeros(lfcc.shape[0], dtype=torch.int64, device=lfcc.device)  # :96
-        _, score = loss_model(feats, labels)  # :104-105
+    labels = torch.zeros(lfcc.shape[0], dtype=torch.int64, device=lfcc.device)  # :96
+    if add_loss in ("ocsoftmax", "p2sgrad"):
+        _, score = loss_model(feats, labels)  # :104-105, :109-110
         return score
-    raise NotImplementedError("scoring with add_loss=%r is off the hot path (amsoftmax / p2sgrad heads)" % (add_loss,))
+    if add_loss == "amsoftmax":
+        logits, _ = loss_model(feats, labels)  # :106-108
+        return ops.softmax_rows(logits)[:, 0]
+    raise NotImplementedError("scoring with add_loss=%r: generate_score.py knows ocsoftmax, amsoftmax and p2sgrad" % (
+        add_loss,))
 
 
 class GraphedScorer:

@@ -230,12 +230,14 @@ class LCNN(nn.Module):
         self.check_input(x)
         x = x.float().contiguous()
         self.arena()
-        feat, _, saved = self._forward_impl(x, save=True)
+        feat, out, saved = self._forward_impl(x, save=True)
+        saved["logits"] = out  # the CE head's input (train.Trainer, add_loss=None)
         return feat, saved
 
-    def backward_saved(self, saved, dfeat):
-        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order."""
-        return self._backward_impl(saved, dfeat, None)
+    def backward_saved(self, saved, dfeat, dout=None):
+        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order.
+        dout: the gradient of saved["logits"] (the CE head), or None."""
+        return self._backward_impl(saved, dfeat, dout)
 
     # ------------------------------------------------------------------ forward
     def _forward_impl(self, x, save):
@@ -302,13 +304,13 @@ class LCNN(nn.Module):
 
         dev = S["x"].device
         ones, zeros = self._units(dev)
-        if dfeat is None:
-            dfeat = torch.zeros_like(S["feat"])
-        dfeat = dfeat.contiguous()
         if dout is not None:  # CE / base-loss branch (main_train.py:355); dead under ang_iso
             dx_mu, _, _ = ops.linear_bwd(S["feat"], self.fc_mu.weight.detach(), dout.contiguous(), True,
                                          dw=gv("fc_mu.weight"), db=gv("fc_mu.bias"))
-            dfeat = ops.add_(dx_mu, dfeat)
+            dfeat = dx_mu if dfeat is None else ops.add_(dx_mu, dfeat.contiguous())
+        if dfeat is None:
+            dfeat = torch.zeros_like(S["feat"])
+        dfeat = dfeat.contiguous()
         l1, l3 = self.out[1], self.out[3]
         B = dfeat.shape[0]
         dh80, _, _ = ops.linear_bwd(S["h80"], l3.weight.detach(), dfeat, True, dw=gv("out.3.weight"), db=gv("out.3.bias"))

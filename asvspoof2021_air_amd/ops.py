@@ -422,6 +422,63 @@ def ocsoftmax_bwd(x, center, labels, r_real, r_fake, alpha, gscale=None, dcenter
     return dx, dcenter
 
 
+def p2sgrad_fwd(x, weight, labels, smooth):
+    B, D = x.shape
+    C = weight.shape[1]
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    neg = torch.empty(B, device=x.device, dtype=torch.float32)
+    _hip.check(_hip.lib().air_p2sgrad_fwd(dptr(x), dptr(weight), dptr(labels, torch.int64), ci(B), ci(D), ci(C),
+                                          cf(smooth), dptr(loss), dptr(neg), stream()), "air_p2sgrad_fwd")
+    return loss, neg
+
+
+def p2sgrad_bwd(x, weight, labels, smooth, gscale=None):
+    B, D = x.shape
+    C = weight.shape[1]
+    dx = torch.empty_like(x)
+    dw = torch.empty_like(weight)
+    _hip.check(_hip.lib().air_p2sgrad_bwd(dptr(x), dptr(weight), dptr(labels, torch.int64), ci(B), ci(D), ci(C),
+                                          cf(smooth), dptr(gscale, allow_none=True), dptr(dx), dptr(dw), stream()),
+               "air_p2sgrad_bwd")
+    return dx, dw
+
+
+def isolate_fwd(x, center, labels, r_real, r_fake, square, want_dist=False):
+    """r_real / r_fake as the module holds them (squared here for IsolateSquareLoss).  want_dist: also |x - c| per
+    row -> (loss, dist)."""
+    B, D = x.shape
+    if square:
+        r_real, r_fake = r_real ** 2, r_fake ** 2
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    dist = torch.empty(B, device=x.device, dtype=torch.float32) if want_dist else None
+    _hip.check(_hip.lib().air_isolate_fwd(dptr(x), dptr(center), dptr(labels, torch.int64), ci(B), ci(D), cf(r_real),
+                                          cf(r_fake), ci(1 if square else 0), dptr(loss),
+                                          dptr(dist, allow_none=True), stream()), "air_isolate_fwd")
+    return (loss, dist) if want_dist else loss
+
+
+def isolate_bwd(x, center, labels, r_real, r_fake, square, gscale=None):
+    B, D = x.shape
+    if square:
+        r_real, r_fake = r_real ** 2, r_fake ** 2
+    dx = torch.empty_like(x)
+    dc = torch.empty_like(center)
+    _hip.check(_hip.lib().air_isolate_bwd(dptr(x), dptr(center), dptr(labels, torch.int64), ci(B), ci(D), cf(r_real),
+                                          cf(r_fake), ci(1 if square else 0), dptr(gscale, allow_none=True), dptr(dx),
+                                          dptr(dc), stream()), "air_isolate_bwd")
+    return dx, dc
+
+
+def amsoftmax_fwd(x, centers, labels, s, m):
+    B, D = x.shape
+    C = centers.shape[0]
+    logits = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    margin = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    _hip.check(_hip.lib().air_amsoftmax_fwd(dptr(x), dptr(centers), dptr(labels, torch.int64), ci(B), ci(D), ci(C),
+                                            cf(s), cf(m), dptr(logits), dptr(margin), stream()), "air_amsoftmax_fwd")
+    return logits, margin
+
+
 def adam_step(p, g, m, v, step, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=5e-4,
               grad_scale=1.0):
     _hip.check(_hip.lib().air_adam_step(dptr(p), dptr(g), dptr(m), dptr(v), csz(p.numel()),

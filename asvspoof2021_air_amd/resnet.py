@@ -309,12 +309,14 @@ class ResNet(nn.Module):
         between backward's bucket boundaries (autograd would run backward on its own worker thread)."""
         x = x.float().contiguous()
         self.arena()
-        feat, _, saved = self._forward_impl(x, None, save=True)
+        feat, mu, saved = self._forward_impl(x, None, save=True)
+        saved["logits"] = mu  # the CE head's input (train.Trainer, add_loss=None)
         return feat, saved
 
-    def backward_saved(self, saved, dfeat):
-        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order."""
-        return self._backward_impl(saved, dfeat, None)
+    def backward_saved(self, saved, dfeat, dout=None):
+        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order.
+        dout: the gradient of saved["logits"] (the CE head), or None."""
+        return self._backward_impl(saved, dfeat, dout)
 
     def _launch_prepack(self, fuse):
         """Enqueue the weight transforms of every conv behind conv1 - Winograd for the 3x3 stride-1 layers, the direct
@@ -493,14 +495,14 @@ class ResNet(nn.Module):
         nm = lambda p: names[id(p)]
         w = lambda conv: conv.weight.detach()
 
-        if dfeat is None:
-            dfeat = torch.zeros_like(S["feat"])
-        dfeat = dfeat.contiguous()
         if dmu is not None:  # CE / base-loss branch (main_train.py:355); dead under ang_iso
             dmu = dmu.contiguous()
             dx_mu, _, _ = ops.linear_bwd(S["feat"], self.fc_mu.weight.detach(), dmu, True,
                                          dw=gv("fc_mu.weight"), db=gv("fc_mu.bias"))
-            dfeat = ops.add_(dx_mu, dfeat)
+            dfeat = dx_mu if dfeat is None else ops.add_(dx_mu, dfeat.contiguous())
+        if dfeat is None:
+            dfeat = torch.zeros_like(S["feat"])
+        dfeat = dfeat.contiguous()
         dpooled, _, _ = ops.linear_bwd(S["pooled"], self.fc.weight.detach(), dfeat, True,
                                        dw=gv("fc.weight"), db=gv("fc.bias"))
         da5, datt = ops.selfatt_pool_bwd(S["a5v"], self.attention.att_weights.detach(), S["noise"],

@@ -1,12 +1,16 @@
-"""Train step of the hot path (main_train.py:310-409 with ``--add_loss ang_iso``):
+"""Train step of the hot path (main_train.py:310-415):
 
     PCM --fused HIP LFCC (+repeat-pad/chop, transposed)--> (B,1,60,feat_len)
-        --ResNet / ECAPA forward--> feat --OC-Softmax--> loss
-        --backward--> gradient arena --[RCCL all-reduce]--> Adam(model) + SGD(centre)
+        --ResNet / ECAPA / LCNN forward--> (feat, logits) --loss head--> loss
+        --backward--> gradient arena --[RCCL all-reduce]--> Adam(model) + SGD(head parameter)
 
 ``Trainer`` sequences the drop-in modules exactly like the reference's loop:
-zero_grad x2, loss.backward(), feat_optimizer.step(), ang_iso_optimizer.step()
-(main_train.py:404-409), LR = lr0 * decay^(epoch // interval) (main_train.py:144-147).
+zero_grad x2, loss.backward(), feat_optimizer.step(), <head>_optimizer.step()
+(main_train.py:352-415), LR = lr0 * decay^(epoch // interval) (main_train.py:144-147).
+
+The head is ``add_loss`` (main_train.py:66-67, :250-300): ``"ang_iso"`` (OC-Softmax, the default here),
+``None`` (the reference's default: cross-entropy on the model's logits, no loss module), ``"isolate"`` /
+``"iso_sq"`` (IsolateLoss / IsolateSquareLoss on the features) or ``"p2sgrad"`` (P2SGradLoss on the features).
 """
 import os
 
@@ -16,7 +20,7 @@ import torch.distributed as td
 
 from . import dist as air_dist
 from .feature_extraction import LFCC
-from .loss import AngularIsoLoss
+from .loss import AngularIsoLoss, IsolateLoss, IsolateSquareLoss, P2SGradLoss
 from .optim import FusedAdam, FusedSGD
 
 
@@ -28,19 +32,52 @@ def adjust_learning_rate(lr0, optimizer, epoch_num, lr_decay=0.5, interval=30):
     return lr
 
 
+ADD_LOSSES = (None, "isolate", "iso_sq", "ang_iso", "p2sgrad")
+# the head a given loss module stands for (any other module: the OC-Softmax head's interface, as before)
+_HEAD_OF_MODULE = ((IsolateSquareLoss, "iso_sq"), (IsolateLoss, "isolate"), (P2SGradLoss, "p2sgrad"))
+
+
+def _make_head(add_loss, enc_dim, r_real, r_fake, alpha):
+    """The loss module main_train.py:255-277 builds for ``--add_loss`` (None: none, the CE head has no parameter)."""
+    if add_loss == "isolate":
+        return IsolateLoss(2, enc_dim, r_real=r_real, r_fake=r_fake)
+    if add_loss == "iso_sq":
+        return IsolateSquareLoss(2, enc_dim, r_real=r_real, r_fake=r_fake)
+    if add_loss == "p2sgrad":
+        return P2SGradLoss(in_dim=enc_dim, out_dim=2, smooth=0.0)
+    if add_loss == "ang_iso":
+        return AngularIsoLoss(enc_dim, r_real=r_real, r_fake=r_fake, alpha=alpha)
+    return None
+
+
 class Trainer:
+    add_loss = "ang_iso"  # (class defaults: the head of a Trainer made without __init__)
+    ce = None
+
     def __init__(self, model, enc_dim=256, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, r_real=0.9,
                  r_fake=0.2, alpha=20.0, weight_loss=1.0, feat_len=750, device="cuda", ecapa=False,
-                 loss_module=None, augment=None, padding="repeat"):
+                 loss_module=None, augment=None, padding="repeat", add_loss="ang_iso"):
+        """add_loss: the training head (module docstring).  An explicit ``loss_module`` of one of the head classes
+        selects its head; any other module is driven as the OC-Softmax head."""
+        if add_loss not in ADD_LOSSES:
+            raise ValueError("add_loss must be one of %s, got %r" % (ADD_LOSSES, add_loss))
+        if loss_module is not None:
+            if add_loss is None:
+                raise ValueError("add_loss=None trains cross-entropy on the logits and takes no loss_module")
+            add_loss = next((h for cls, h in _HEAD_OF_MODULE if isinstance(loss_module, cls)), add_loss)
+        self.add_loss = add_loss
         self.device = torch.device(device)
         self.model = model.to(self.device)
-        self.loss = (loss_module if loss_module is not None else
-                     AngularIsoLoss(enc_dim, r_real=r_real, r_fake=r_fake, alpha=alpha)).to(self.device)
+        head = loss_module if loss_module is not None else _make_head(add_loss, enc_dim, r_real, r_fake, alpha)
+        self.loss = head.to(self.device) if head is not None else None
+        if add_loss is None:
+            from .adversarial import CrossEntropyLoss
+            self.ce = CrossEntropyLoss()  # main_train.py:251
         self.lfcc = LFCC(320, 160, 512, 16000, 20, with_energy=False).to(self.device)
         self.lfcc.mutate_input = False
         self.lr0 = lr
         self.feat_optimizer = FusedAdam(self.model, lr=lr, betas=betas, eps=eps, weight_decay=0.0005)
-        self.loss_optimizer = FusedSGD(self.loss, lr=lr)
+        self.loss_optimizer = FusedSGD(self.loss, lr=lr) if self.loss is not None else None
         self.weight_loss = weight_loss
         self.feat_len = feat_len
         self.ecapa = ecapa
@@ -77,7 +114,7 @@ class Trainer:
         if self.world == 1:
             return
         td.broadcast(self.model.arena().flat, src=0)
-        for p in self.loss.parameters():
+        for p in self._loss_params():
             td.broadcast(p.data, src=0)
         self.sync_buffers_from_rank0()
 
@@ -88,6 +125,9 @@ class Trainer:
             return
         for b in self.model.buffers():
             td.broadcast(b.data, src=0)
+
+    def _loss_params(self):
+        return list(self.loss.parameters()) if self.loss is not None else []
 
     # ------------------------------------------------------------------ logs and checkpoints
     def set_out_fold(self, out_fold, fresh=True):
@@ -105,7 +145,8 @@ class Trainer:
 
     def log_step(self, epoch_num, i, loss, adv=None):
         """One line of ``train_loss.log`` exactly as main_train.py:479-481 appends it per iteration:
-        ``str(epoch) \\t str(i) \\t str(loss) \\n`` with ``loss`` the Python float of ``.item()``.  ``adv``:
+        ``str(epoch) \\t str(i) \\t str(loss) \\n`` with ``loss`` the Python float of ``.item()`` - the head's own
+        loss before ``weight_loss`` (trainlossDict[monitor_loss][-1], main_train.py:287-290, :359-415), as step returns it.  ``adv``:
         the (adv_loss, acc_1, acc_2) triple of the ``--ADV_AUG`` variant (main_train.py:470-476)."""
         if self.out_fold is None or air_dist.rank() != 0:
             return
@@ -130,7 +171,7 @@ class Trainer:
         (main_train.py:671-709): ``checkpoint/anti-spoofing_feat_model_%d.pt`` and
         ``checkpoint/anti-spoofing_loss_model_%d.pt`` every epoch (numbered epoch_num + 1), and
         ``anti-spoofing_feat_model.pt`` / ``anti-spoofing_loss_model.pt`` whenever the validation loss
-        improves.  generate_score.py:46-48 loads these with torch.load.  Returns True when the best pair
+        improves.  The CE head (add_loss=None) has no loss module and writes no loss-model file.  generate_score.py:46-48 loads these with torch.load.  Returns True when the best pair
         was written.
 
         No collective runs in here, so the usual ``if rank == 0: trainer.save_checkpoint(...)`` is safe with
@@ -145,10 +186,12 @@ class Trainer:
         if air_dist.rank() == 0:
             ck = os.path.join(self.out_fold, "checkpoint")
             torch.save(self.model, os.path.join(ck, "anti-spoofing_feat_model_%d.pt" % (epoch_num + 1)))
-            torch.save(self.loss, os.path.join(ck, "anti-spoofing_loss_model_%d.pt" % (epoch_num + 1)))
+            if self.loss is not None:
+                torch.save(self.loss, os.path.join(ck, "anti-spoofing_loss_model_%d.pt" % (epoch_num + 1)))
             if improved:
                 torch.save(self.model, os.path.join(self.out_fold, "anti-spoofing_feat_model.pt"))
-                torch.save(self.loss, os.path.join(self.out_fold, "anti-spoofing_loss_model.pt"))
+                if self.loss is not None:
+                    torch.save(self.loss, os.path.join(self.out_fold, "anti-spoofing_loss_model.pt"))
         if improved:
             self.prev_loss = val_loss
             self.early_stop_cnt = 0
@@ -173,30 +216,73 @@ class Trainer:
         return cnt >= patience
 
     def set_epoch(self, epoch_num, lr_decay=0.5, interval=30):
+        """main_train.py:287-300.  Quirk kept: the reference never decays the ``iso_sq`` head's SGD learning rate
+        (its adjust_learning_rate calls name isolate, ang_iso and p2sgrad only)."""
         adjust_learning_rate(self.lr0, self.feat_optimizer, epoch_num, lr_decay, interval)
-        adjust_learning_rate(self.lr0, self.loss_optimizer, epoch_num, lr_decay, interval)
+        if self.loss_optimizer is not None and self.add_loss != "iso_sq":
+            adjust_learning_rate(self.lr0, self.loss_optimizer, epoch_num, lr_decay, interval)
 
     def features(self, pcm, start=None):
         """(B, L) PCM -> model input, fused on the GPU (dataset.py:66-79 + main_train.py:338,:347)."""
         feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, 60, feat_len)
         return feat if self.ecapa else feat.unsqueeze(1)
 
+    def _head(self, feats, logits, labels):
+        """The head's forward: (loss as logged, the loss backward() starts from, second output).  Second output:
+        -scores (ang_iso, p2sgrad), the logits (CE), None (isolate / iso_sq: the reference's head returns a bare loss)."""
+        if self.add_loss is None:
+            loss = self.ce(logits, labels)
+            return loss, loss, logits.detach()  # main_train.py:352-362: no weight_loss
+        if self.add_loss in ("isolate", "iso_sq"):
+            loss, second = self.loss(feats, labels), None
+        else:
+            loss, second = self.loss(feats, labels)
+        if self.add_loss == "p2sgrad" or self.weight_loss == 1.0:  # main_train.py:411-415: p2sgrad has no weight_loss
+            return loss, loss, second
+        return loss, loss * self.weight_loss, second  # main_train.py:365-366, :376
+
+    def _zero_grads(self):
+        self.feat_optimizer.zero_grad()
+        if self.loss_optimizer is not None:
+            self.loss_optimizer.zero_grad()
+
+    def _optimise(self, scale):
+        self.feat_optimizer.step(grad_scale=scale)
+        if self.loss_optimizer is not None:
+            self.loss_optimizer.step(grad_scale=scale)
+
     def step_features(self, feat, labels):
-        """One optimisation step on model-layout features.  Returns (loss, -scores)."""
+        """One optimisation step on model-layout features.  Returns (loss, second output of the head: -scores for
+        ang_iso / p2sgrad, the logits for the CE head, None for isolate / iso_sq)."""
         if not self.model.training:  # (Module.train() walks every submodule: 1 ms of host time per step)
             self.model.train()
-        self.feat_optimizer.zero_grad()
-        self.loss_optimizer.zero_grad()
-        feats, _ = self.model(feat)
-        loss, neg_scores = self.loss(feats, labels)
-        (loss if self.weight_loss == 1.0 else loss * self.weight_loss).backward()  # main_train.py:376, :406
+        self._zero_grads()
+        feats, logits = self.model(feat)
+        loss, bwd, second = self._head(feats, logits, labels)
+        bwd.backward()  # main_train.py:356-415
         scale = 1.0
         if self.world > 1:
             air_dist.allreduce_grads(self.model, self.loss)
             scale = 1.0 / self.world
-        self.feat_optimizer.step(grad_scale=scale)
-        self.loss_optimizer.step(grad_scale=scale)
-        return loss.detach(), neg_scores
+        self._optimise(scale)
+        return loss.detach(), second
+
+    @torch.no_grad()
+    def eval_batch(self, pcm, labels, start=None):
+        """The dev pass of main_train.py:526-575 for one batch: (loss, score) with the reference's score of each head -
+        softmax(logits)[:, 0] (None), |feats - center| (isolate / iso_sq), the head's second output (ang_iso, p2sgrad).
+        Eval-mode model; feeds ``save_checkpoint(val_loss=...)`` for any head."""
+        from . import ops
+        self.model.eval()
+        feats, logits = self.model(self.features(pcm, start))
+        labels = labels.to(device=feats.device, dtype=torch.int64).contiguous()
+        if self.add_loss is None:
+            return self.ce(logits, labels), ops.softmax_rows(logits)[:, 0]
+        if self.add_loss in ("isolate", "iso_sq"):
+            lm = self.loss
+            return ops.isolate_fwd(feats.float().contiguous(), lm.center.detach().contiguous(), labels, float(lm.r_real),
+                                   float(lm.r_fake), self.add_loss == "iso_sq", want_dist=True)
+        return self.loss(feats, labels)
 
     def step(self, pcm, labels, start=None):
         if self.augment is not None:
@@ -254,13 +340,22 @@ class Trainer:
         if had:
             ops.unpin_workspaces(id(self))
 
+    def _head_scalars(self):
+        """The head's scalars that travel as kernel arguments (ang_iso: the tuple the key always held)."""
+        if self.add_loss == "ang_iso":
+            return (float(self.loss.r_real), float(self.loss.r_fake), float(self.loss.alpha))
+        if self.add_loss in ("isolate", "iso_sq"):
+            return (self.add_loss, float(self.loss.r_real), float(self.loss.r_fake))
+        if self.add_loss == "p2sgrad":
+            return ("p2sgrad", float(self.loss.smooth))
+        return ("ce",)
+
     def _graph_key(self, pcm, labels):
         """Everything a capture freezes: shapes, the arithmetic mode and the scalars that travel as kernel
-        arguments (loss weight and the OC-Softmax margins / scale)."""
+        arguments (loss weight and the head's own: OC-Softmax margins / scale, Isolate radii, P2SGrad smoothing)."""
         return (tuple(pcm.shape), pcm.dtype, tuple(labels.shape), getattr(self.model, "compute_dtype", "fp32"),
-                self.feat_len, float(self.weight_loss), float(self.loss.r_real), float(self.loss.r_fake),
-                float(self.loss.alpha), self.padding, getattr(self.model, "noise_mode", None),
-                getattr(self.model, "noise_scale", None))
+                self.feat_len, float(self.weight_loss)) + self._head_scalars() + (
+                self.padding, getattr(self.model, "noise_mode", None), getattr(self.model, "noise_scale", None))
 
     def _graphed_step(self, pcm, labels):
         from . import ops
@@ -284,7 +379,7 @@ class Trainer:
         if not self.model.training:  # an interleaved score() left eval mode behind
             self.model.train()
         # The captured kernels write the gradients into the tensors that were p.grad AT CAPTURE (arena views for the
-        # model, a tensor of the graph's private pool for the loss centre).  Any eager step or zero_grad() since then
+        # model, a tensor of the graph's private pool for the loss head's parameter).  Any eager step or zero_grad() since then
         # replaced or dropped them: re-point every p.grad, or the optimisers would apply stale / no gradients.
         for p, gr in g["grads"]:
             if p.grad is not gr:
@@ -316,9 +411,8 @@ class Trainer:
             finally:
                 self.model._bucketer = None
             scale = 1.0 / self.world
-        self.feat_optimizer.step(grad_scale=scale)
-        self.loss_optimizer.step(grad_scale=scale)
-        return g["loss"].detach().clone(), g["neg"].clone()
+        self._optimise(scale)
+        return g["loss"].detach().clone(), (g["neg"].clone() if g["neg"] is not None else None)
 
     def _capture_or_fall_back(self, key, pcm, labels):
         """The capture, guarded for world > 1: were it to fail on ANY rank (a runtime that refuses a call inside a
@@ -346,20 +440,26 @@ class Trainer:
 
     def _fwd_bwd_direct(self, pcm, labels):
         """front-end + forward + loss + backward as plain calls in THIS thread (what model(x) -> loss.backward() does
-        through autograd, whose backward runs on a worker thread): (loss, -scores, [(param, grad)])."""
+        through autograd, whose backward runs on a worker thread): (loss, second output, [(param, grad)])."""
         model = self.model
         feats, saved = model.forward_saved(self.features(pcm, None))
-        leaf = feats.detach().requires_grad_(True)
-        loss, neg = self.loss(leaf, labels)
-        (loss if self.weight_loss == 1.0 else loss * self.weight_loss).backward()  # the OC-Softmax head only: d(loss) / d(feats) and the centre's gradient
-        grads = model.backward_saved(saved, leaf.grad)
+        if self.add_loss is None:  # the CE head: the gradient enters through the logits (fc_mu / fc7, bn7)
+            leaf = saved["logits"].detach().requires_grad_(True)
+            loss, bwd, second = self._head(None, leaf, labels)
+            bwd.backward()
+            grads = model.backward_saved(saved, None, dout=leaf.grad)
+        else:
+            leaf = feats.detach().requires_grad_(True)
+            loss, bwd, second = self._head(leaf, None, labels)
+            bwd.backward()  # the head only: d(loss) / d(feats) and its parameter's gradient
+            grads = model.backward_saved(saved, leaf.grad)
         pairs = []
         for (n, p, _, _), gr in zip(model.arena().entries, grads):
             if gr is not None:
                 p.grad = gr
                 pairs.append((p, gr))
-        pairs += [(p, p.grad) for p in self.loss.parameters() if p.grad is not None]
-        return loss, neg, pairs
+        pairs += [(p, p.grad) for p in self._loss_params() if p.grad is not None]
+        return loss, second, pairs
 
     def _capture(self, key, pcm, labels):
         """The step recorded through _fwd_bwd_direct on a capture stream: one hipGraph, or (graph_segments) several sharing
@@ -367,8 +467,7 @@ class Trainer:
         from . import ops
         self.model.train()
         s_pcm, s_labels = pcm.detach().clone(), labels.detach().clone()
-        self.feat_optimizer.zero_grad()
-        self.loss_optimizer.zero_grad()
+        self._zero_grads()
         arena = self.model.arena()
         pool = torch.cuda.graph_pool_handle()
         state = {"g": None, "hi": arena.head_total}
@@ -427,9 +526,9 @@ class Trainer:
 
     @torch.no_grad()
     def score(self, pcm, start=None):
-        """generate_score.py:91-105: returns +cos similarity (the value written to the score file)."""
+        """generate_score.py:91-110: the value written to the score file (+cos similarity for ang_iso and p2sgrad,
+        softmax(logits)[:, 0] for the CE head - and for isolate / iso_sq, which generate_score.py has no branch for)."""
+        from .generate_score import batch_scores
         self.model.eval()
-        feats, _ = self.model(self.features(pcm, start))
-        labels = torch.zeros(feats.shape[0], dtype=torch.int64, device=feats.device)
-        _, neg = self.loss(feats, labels)
-        return -neg
+        add = {"ang_iso": "ocsoftmax", "p2sgrad": "p2sgrad"}.get(self.add_loss)
+        return -batch_scores(self.model, self.features(pcm, start), self.loss, add)

@@ -762,6 +762,35 @@ int air_ocsoftmax_bwd(const float* x, const float* center, const int64_t* labels
                       float r_real, float r_fake, float alpha, const float* gscale_dev,
                       float* dx, float* dcenter, air_stream_t stream);
 
+/* ------------------------------------------------- other loss heads ---
+ * csrc/loss_heads.hip.  One workgroup each, per-row terms summed in a fixed order (no atomics: deterministic);
+ * x (B,D) fp32, labels (B,) int64, B <= 4096, else AIR_EUNSUPPORTED.  bwd: gradients of loss * gscale
+ * (gscale_dev: device scalar or NULL for 1).
+ *
+ * P2SGradLoss.forward (loss.py:300-335): w = weight.renorm(2, 1, 1e-5).mul(1e5) (weight (D,C), C <= 4,
+ * D <= 1024), cos = clamp(x w / |x|, -1, 1) with no epsilon on |x| (:314-325), target = one-hot smoothed by
+ * `smooth` (:291-297, :331), loss = MSE(cos, target) averaged over B x C (:333); neg_cos0 = -cos[:, 0] (:335).
+ * bwd: dx (B,D) and dweight (D,C) through renorm as torch autograd differentiates it (scale and column-norm
+ * term); clamp passes the gradient where -1 <= cos <= 1. */
+int air_p2sgrad_fwd(const float* x, const float* weight, const int64_t* labels, int B, int D, int C, float smooth,
+                    float* loss, float* neg_cos0, air_stream_t stream);
+int air_p2sgrad_bwd(const float* x, const float* weight, const int64_t* labels, int B, int D, int C, float smooth,
+                    const float* gscale_dev, float* dx, float* dweight, air_stream_t stream);
+/* IsolateLoss.forward (loss.py:119-139): relu(|x - c| - r_real) averaged over the label-0 rows plus
+ * relu(r_fake - |x - c|) averaged over the label-1 rows; square != 0: IsolateSquareLoss (:155-173), squared norms
+ * with r_real, r_fake passed ALREADY SQUARED.  A class without rows gives NaN (torch's mean of an empty tensor).
+ * center (1,D).  dist_or_null: (B,) |x - c| (main_train.py:548's dev-pass score) or NULL.
+ * bwd: dx (B,D), dcenter (1,D); the norm's gradient is 0 at |x - c| == 0 and a ReLU input of 0 passes none. */
+int air_isolate_fwd(const float* x, const float* center, const int64_t* labels, int B, int D, float r_real,
+                    float r_fake, int square, float* loss, float* dist_or_null, air_stream_t stream);
+int air_isolate_bwd(const float* x, const float* center, const int64_t* labels, int B, int D, float r_real,
+                    float r_fake, int square, const float* gscale_dev, float* dx, float* dcenter,
+                    air_stream_t stream);
+/* AMSoftmax.forward (loss.py:217-234), forward only: logits (B,C) = cosine of the rows of x and of centers (C,D),
+ * no epsilon; margin_logits = s * (logits - m * onehot(labels)). */
+int air_amsoftmax_fwd(const float* x, const float* centers, const int64_t* labels, int B, int D, int C, float s,
+                      float m, float* logits, float* margin_logits, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

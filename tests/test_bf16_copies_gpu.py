@@ -141,6 +141,48 @@ def test_pointwise_bf16_tiles_vs_bf16_reference(ops, cfg):
     close(ops.conv1d_wgrad(x.cuda(), dy.cuda(), (Cout, Cin, 1), bf16=True), dw, 2e-5, "wgrad")
 
 
+def _device_kernels(fn):
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    return out, {ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA}
+
+
+@pytest.mark.parametrize("opts,kernel,absent", [
+    (dict(C1B_PS=0), "c1b_fwd_kernel", "c1b_fwd_ps"),           # register-staged forward / dgrad, no persistent kernel
+    (dict(C1B_PS=1), "c1b_fwd_ps_kernel", "c1b_fwd_ps2_kernel"),  # persistent 128-row tiles only
+    (dict(C1B_PS=3), "c1b_fwd_ps_kernel", "c1b_fwd_ps2_kernel"),  # + 256-row tiles
+    (dict(C1B_PS=5), "c1b_fwd_ps2_kernel", "c1b_fwd_kernel"),     # 256 x 256 tiles
+    (dict(C1B_GEMM_PS=0), "c1b_gemm_kernel", "c1b_gemm_ps_kernel"),  # weight gradient without the persistent GEMM
+])
+@pytest.mark.parametrize("cfg", [(2, 512, 512, 750), (2, 1536, 256, 300)])
+def test_pointwise_bf16_dispatch_options_vs_bf16_reference(ops, cfg, opts, kernel, absent):
+    """Options C1B_PS / C1B_GEMM_PS pick other pointwise kernels; each holds the same bound against fp64 of the
+    bf16-rounded operands, and the kernel the option selects is the one that runs."""
+    from asvspoof2021_air_amd import _hip
+    B, Cin, Cout, T = cfg
+    x = synth_feat((B, Cin, T), 1)
+    w = synth_feat((Cout, Cin, 1), 2, scale=0.05)
+    b = synth_feat((Cout,), 3, scale=0.2)
+    dy = synth_feat((B, Cout, T), 4)
+    rnd = lambda t: t.to(torch.bfloat16).double()
+    names = set()
+    with _hip.options(**opts):
+        got, n = _device_kernels(lambda: ops.conv1d_fwd(x.cuda(), w.cuda(), b.cuda(), relu=True, bf16=True))
+        names |= n
+        close(got, F.relu(F.conv1d(rnd(x), rnd(w), b.double())), 2e-5, "fwd")
+        got, n = _device_kernels(lambda: ops.conv1d_dgrad(dy.cuda(), w.cuda(), bf16=True))
+        names |= n
+        close(got, F.conv_transpose1d(rnd(dy), rnd(w)), 2e-5, "dgrad")
+        got, n = _device_kernels(lambda: ops.conv1d_wgrad(x.cuda(), dy.cuda(), (Cout, Cin, 1), bf16=True))
+        names |= n
+        close(got, torch.einsum("bot,bit->oi", rnd(dy), rnd(x)).unsqueeze(2), 2e-5, "wgrad")
+    assert any(kernel + "<" in k or kernel + "(" in k for k in names), (kernel, sorted(names))
+    assert not any(absent in k for k in names), (absent, sorted(names))
+
+
 @pytest.mark.parametrize("shape", [(128, 3072, 1), (64, 128, 1), (5, 33, 7), (4, 16, 750), (3, 8, 3375), (2, 4, 751)])
 def test_batchnorm_access_paths(ops, shape):
     """Planes of one element (flat kernels), short planes, 8-byte-aligned even planes, odd planes (head peeled)."""

@@ -50,6 +50,7 @@ CONVS = [
     (2, 256, 5, 47, 512, (1, 1), 2, (0, 0)),    # layer4.0.shortcut-like
     (2, 512, 3, 94, 256, (3, 3), 1, (0, 1)),    # conv5
     (3, 512, 3, 47, 256, (3, 3), 1, (0, 1)),    # conv5 geometry, odd width (dgrad = three 1x3 row convs)
+    (4, 48, 15, 94, 128, (3, 3), 1, (1, 1)),    # LCNN conv5: 48 input channels, the weight gradient on x zero-padded to 64
 ]
 
 
@@ -549,6 +550,7 @@ WINO = [
     (5, 64, 18, 750, 64),     # wgrad: 24 stages per tile row, right edge inside a lane chunk
     (7, 128, 9, 375, 64),     # odd W: columns W and W+1 are both seen by the last tile
     (3, 64, 4, 33, 128),
+    (4, 64, 6, 4, 64),        # W = 4: the narrowest image F(4x4 | 3x4, 3x3) takes (W = 3 runs F(2x2, 3x3))
 ]
 
 

@@ -131,11 +131,13 @@ def test_forward_vs_golden_b2(golden):
             assert int(v.item()) == 1
 
 
-@pytest.mark.parametrize("B", [2, 8])
+@pytest.mark.parametrize("B", [2, 8, 64])
 def test_forward_and_grads_vs_fp64(B):
     """Forward train + eval against the fp64 restatement; every parameter gradient against an fp64 backward that took
     the GPU's own MFM / pool decisions.  The decisions that differ from fp64's own (rounding near a tie) are counted:
-    they must be rare, and the distance of the full fp64 run is then what they explain."""
+    they must be rare, and the distance of the full fp64 run is then what they explain.  B = 64 is the reference's
+    training batch: the launch shapes the model trains with (split counts, pixel tiles, the zero-padded 48-channel
+    weight gradients)."""
     x = synth_feat((B, 1, 60, 750), seed=40 + B)
     m = _model()
     gk = torch.Generator().manual_seed(50 + B)
@@ -300,6 +302,42 @@ def test_full_size_step():
     torch.cuda.synchronize()
     assert np.isfinite(loss.item()) and torch.isfinite(neg).all()
     assert torch.isfinite(m.arena().flat).all()
+
+
+def test_full_size_step_vs_fp64():
+    """One Trainer step at the reference's training size (B = 64, 4 s, feat_len 750) on a fixed dropout mask: its loss
+    and scores (pre-update, as step 1 of test_trainer_eager_step_and_trajectory_vs_fp64) against fp64 evaluated with
+    the GPU's own MFM / pool decisions, taken by a twin model's forward on the same input; the decisions fp64 would take
+    otherwise are counted.  The gradients at B = 64: test_forward_and_grads_vs_fp64[64]."""
+    B = 64
+    gk = torch.Generator().manual_seed(9)
+    keep = (torch.rand(B, 4416, generator=gk) >= 0.7).float() / 0.3
+    m, twin = _model(), _model()
+    m.set_dropout_mask(keep)
+    twin.set_dropout_mask(keep)
+    tr = _trainer(m)
+    pcm = synth_pcm(B, 64000, seed=9).cuda()
+    labels = (torch.arange(B) % 2).cuda()
+    x = tr.features(pcm)
+    twin.train()
+    _, saved = twin.forward_saved(x)
+    torch.cuda.synchronize()
+    routes = {"conv1": saved["r1"].cpu(), "head": saved["rh"].cpu().view(B, 80, 1, 1)}
+    for ent in saved["layers"]:
+        routes[ent[0]] = ent[5].cpu()
+    p64 = {k: v.detach().cpu().double() for k, v in m.named_parameters()}
+    b64 = _oracle_bufs(m)
+    loss, neg = tr.step(pcm, labels)
+    torch.cuda.synchronize()
+    assert np.isfinite(loss.item()) and torch.isfinite(neg).all()
+    with torch.no_grad():
+        f64, _, own = o.forward(p64, x.cpu().double(), True, keep=keep, buffers=b64, routes=routes)
+        l64, n64 = o.ocsoftmax(f64, fill_value("center", (1, 256)).double(), labels.cpu())
+    flips = sum(int((own[k] != routes[k]).sum()) for k in routes)
+    total = sum(v.numel() for v in routes.values())
+    assert flips <= 1e-4 * total, (flips, total)
+    np.testing.assert_allclose(loss.item(), l64.item(), rtol=1e-4)
+    np.testing.assert_allclose(neg.cpu().numpy(), n64.numpy(), atol=1e-4)
 
 
 def _aten_kernels_per_step(tr, pcm, labels, steps=2):

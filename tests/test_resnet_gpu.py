@@ -353,8 +353,10 @@ def test_preact_block_standalone_forward(stride, cin, cout, training):
 
 def test_long_utterance_beyond_lds_pooling():
     """resnet.py:23-46 pools any length; beyond T' = 148 pooled frames (about 1190 input frames) the map no longer
-    fits the pooling kernel's LDS and its in-place variant takes over: forward against the oracle, and a train step
-    runs (12 s utterance = 1201 frames -> T' = 151)."""
+    fits the pooling kernel's LDS and its in-place variant takes over: forward against the oracle, and the gradients
+    of a train-mode backward (12 s utterance = 1201 frames -> T' = 151) against the oracle's fp64 backward of the same
+    loss, with the per-tensor bound of tests/test_full_size_gpu.py (relative L2 within 3x the fp32 oracle's own
+    distance to fp64 plus twice the default path's slack)."""
     m = make_model().eval()
     m.set_attention_noise(None)
     x = synth_feat((2, 1, 60, 1201), seed=77)
@@ -366,6 +368,28 @@ def test_long_utterance_beyond_lds_pooling():
     feat, _ = m(x.cuda())
     feat.square().mean().backward()
     assert torch.isfinite(m.conv1.weight.grad).all() and float(m.conv1.weight.grad.abs().max()) > 0
+    grads = {k: p.grad.detach().cpu().double() for k, p in m.named_parameters() if p.grad is not None}
+
+    def oracle_grads(dtype):
+        state = fill_state(o_resnet.resnet18_shapes())
+        p = {k: (v.to(dtype) if v.dtype.is_floating_point else v) for k, v in state.items()}
+        for k in grads:
+            p[k].requires_grad_(True)
+        fo, _ = o_resnet.resnet18_forward(p, x.to(dtype), training=True, noise=None, updates={})
+        fo.square().mean().backward()
+        assert {k for k, v in p.items() if getattr(v, "grad", None) is not None} == set(grads)
+        return {k: p[k].grad.double() for k in grads}
+
+    g64, g32 = oracle_grads(torch.float64), oracle_grads(torch.float32)
+    slack = 2.0 * tol("full_size_slack", "default")
+    worst = ("", 0.0, 0.0)
+    for k, gh in grads.items():
+        nrm = float(g64[k].norm()) + 1e-30
+        e_hip, e_cpu = float((gh - g64[k]).norm()) / nrm, float((g32[k] - g64[k]).norm()) / nrm
+        assert e_hip <= 3.0 * e_cpu + slack, (k, e_hip, e_cpu, slack)
+        if e_hip > worst[1]:
+            worst = (k, e_hip, e_cpu)
+    record("resnet_long_utterance_worst_grad", list(worst))
 
 
 def _graph_trainer(graph, seed=4242):

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _hip
-from ._hip import AirConv1d, AirConv2d, ci, cf, csz, dptr, stream
+from ._hip import AirConv1d, AirConv2d, AirConvNarrow, ci, cf, csz, dptr, stream
 
 _WS = {}
 _WS_GEN = [0]     # bumped whenever a scratch buffer is (re)allocated
@@ -602,6 +602,168 @@ def dropout_mask_ctr(shape, p, seed, counter, device):
     _hip.check(_hip.lib().air_dropout_mask_ctr(dptr(keep), csz(keep.numel()), cf(p), ctypes.c_uint64(seed),
                                                dptr(counter, torch.int64), stream()), "air_dropout_mask_ctr")
     return keep
+
+
+# ------------------------------------------------------------------ Res2Net (res2net.py)
+def sptr(t):
+    """(pointer, batch stride) of a (B, C, H, W) fp32 GPU tensor or channel-slice view whose (C, H, W) block is
+    dense."""
+    if t.dim() != 4 or not t.is_cuda or t.dtype != torch.float32:
+        raise _hip.AirError("expected a (B, C, H, W) fp32 GPU tensor")
+    B, C, H, W = t.shape
+    if t.stride(3) != 1 or (H > 1 and t.stride(2) != W) or (C > 1 and t.stride(1) != H * W):
+        raise _hip.AirError("channel-slice view must keep (C, H, W) dense")
+    return ctypes.c_void_p(t.data_ptr()), (t.stride(0) if B > 1 else C * H * W)
+
+
+def _narrow_desc(x_shape, cout, k, stride, x_bs=0, y_bs=0):
+    B, Cin, H, W = x_shape
+    if k not in (1, 3):
+        raise _hip.AirError("conv_narrow: kernel %d (1 or 3 only)" % k)
+    pad = k // 2
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    return AirConvNarrow(B, Cin, H, W, cout, k, stride, Ho, Wo, x_bs, y_bs)
+
+
+def conv_narrow_fwd(x, w, stride=1, in_scale=None, in_shift=None, relu=False, out=None):
+    """y = conv2d(act(x), w, stride, padding=k // 2) on the narrow-channel kernels; act = optional x*in_scale + in_shift
+    (+ ReLU).  x and ``out`` may be channel-slice views."""
+    xp, xb = sptr(x)
+    d = _narrow_desc(x.shape, w.shape[0], w.shape[2], stride, xb)
+    if out is None:
+        out = torch.empty((d.B, d.Cout, d.Ho, d.Wo), device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (d.B, d.Cout, d.Ho, d.Wo):
+        raise _hip.AirError("conv_narrow_fwd: out is %s, want %s" % (tuple(out.shape), (d.B, d.Cout, d.Ho, d.Wo)))
+    yp, yb = sptr(out)
+    d.y_bstride = yb
+    _hip.check(_hip.lib().air_conv_narrow_fwd(ctypes.byref(d), xp, dptr(w), dptr(in_scale, allow_none=True),
+                                              dptr(in_shift, allow_none=True), ci(1 if relu else 0), yp, stream()),
+               "air_conv_narrow_fwd")
+    return out
+
+
+def conv_narrow_dgrad(dy, w, x_shape, stride=1, out=None, accumulate=False):
+    """Gradient with respect to conv_narrow_fwd's (activated) input; ``out`` (may be a channel-slice view) is written,
+    or added to with accumulate."""
+    d = _narrow_desc(tuple(x_shape), w.shape[0], w.shape[2], stride)
+    if accumulate and out is None:
+        raise _hip.AirError("conv_narrow_dgrad: accumulate needs out")
+    if out is None:
+        out = torch.empty(tuple(x_shape), device=dy.device, dtype=torch.float32)
+    gp, gb = sptr(dy)
+    xp, xb = sptr(out)
+    if tuple(dy.shape) != (d.B, d.Cout, d.Ho, d.Wo) or tuple(out.shape) != tuple(x_shape):
+        raise _hip.AirError("conv_narrow_dgrad: shapes dy %s / dx %s do not match" % (tuple(dy.shape), tuple(out.shape)))
+    d.x_bstride, d.y_bstride = xb, gb
+    _hip.check(_hip.lib().air_conv_narrow_dgrad(ctypes.byref(d), gp, dptr(w), xp, ci(1 if accumulate else 0),
+                                                stream()), "air_conv_narrow_dgrad")
+    return out
+
+
+def conv_narrow_wgrad(x, dy, w_shape, stride=1, in_scale=None, in_shift=None, relu=False, out=None):
+    """dw (Cout, Cin, k, k) of conv_narrow_fwd (same prologue); deterministic.  x and dy may be channel-slice views."""
+    xp, xb = sptr(x)
+    gp, gb = sptr(dy)
+    d = _narrow_desc(x.shape, w_shape[0], w_shape[2], stride, xb, gb)
+    if tuple(dy.shape) != (d.B, d.Cout, d.Ho, d.Wo):
+        raise _hip.AirError("conv_narrow_wgrad: dy is %s, want %s" % (tuple(dy.shape), (d.B, d.Cout, d.Ho, d.Wo)))
+    dw = out if out is not None else torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+    n = int(_hip.lib().air_conv_narrow_wgrad_ws_bytes(ctypes.byref(d)))
+    if n == 0:
+        raise _hip.AirError("conv_narrow_wgrad: unsupported shape %s -> %s" % (tuple(x.shape), tuple(w_shape)))
+    ws = workspace(n, x.device)
+    _hip.check(_hip.lib().air_conv_narrow_wgrad(ctypes.byref(d), xp, gp, dptr(in_scale, allow_none=True),
+                                                dptr(in_shift, allow_none=True), ci(1 if relu else 0), dptr(dw),
+                                                dptr(ws, torch.uint8), csz(n), stream()), "air_conv_narrow_wgrad")
+    return dw
+
+
+def res2_bn_relu_apply(x, scale, shift, y1, add=None, y2=None):
+    """y1 (channel-slice view) = relu(x*scale + shift); y2 (dense) = that + add (channel-slice view).  4-D tensors;
+    x may be a channel slice too."""
+    B, C, H, W = x.shape
+    xp, xb = sptr(x)
+    y1p, y1b = sptr(y1)
+    ap, ab = sptr(add) if add is not None else (ctypes.c_void_p(0), 0)
+    _hip.check(_hip.lib().air_res2_bn_relu_apply(xp, csz(xb), ci(B), ci(C), ci(H * W), dptr(scale), dptr(shift), y1p,
+                                                 csz(y1b), ap, csz(ab), dptr(y2, allow_none=True), stream()),
+               "air_res2_bn_relu_apply")
+    return y2
+
+
+def pool_out_size(n, k, stride, pad, ceil_mode):
+    """PyTorch's pooling output size."""
+    num = n + 2 * pad - k
+    o = (-(-num // stride) if ceil_mode else num // stride) + 1
+    if ceil_mode and (o - 1) * stride >= n + pad:
+        o -= 1
+    return o
+
+
+def avgpool2d_fwd(x, k, stride, pad, ceil_mode, count_include_pad, out=None):
+    """nn.AvgPool2d forward; x and ``out`` may be channel-slice views."""
+    B, C, H, W = x.shape
+    Ho, Wo = pool_out_size(H, k, stride, pad, ceil_mode), pool_out_size(W, k, stride, pad, ceil_mode)
+    if out is None:
+        out = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    xp, xb = sptr(x)
+    yp, yb = sptr(out)
+    _hip.check(_hip.lib().air_avgpool2d_fwd(xp, csz(xb), ci(B), ci(C), ci(H), ci(W), ci(k), ci(stride), ci(pad),
+                                            ci(1 if ceil_mode else 0), ci(1 if count_include_pad else 0), ci(Ho),
+                                            ci(Wo), yp, csz(yb), stream()), "air_avgpool2d_fwd")
+    return out
+
+
+def avgpool2d_bwd(dy, x_shape, k, stride, pad, ceil_mode, count_include_pad, out=None, accumulate=False):
+    """Gradient of avgpool2d_fwd with respect to x (``out`` may be a channel-slice view; accumulate adds to it)."""
+    B, C, H, W = x_shape
+    Ho, Wo = dy.shape[2], dy.shape[3]
+    if accumulate and out is None:
+        raise _hip.AirError("avgpool2d_bwd: accumulate needs out")
+    if out is None:
+        out = torch.empty(tuple(x_shape), device=dy.device, dtype=torch.float32)
+    gp, gb = sptr(dy)
+    xp, xb = sptr(out)
+    _hip.check(_hip.lib().air_avgpool2d_bwd(gp, csz(gb), ci(B), ci(C), ci(H), ci(W), ci(k), ci(stride), ci(pad),
+                                            ci(1 if ceil_mode else 0), ci(1 if count_include_pad else 0), ci(Ho),
+                                            ci(Wo), xp, csz(xb), ci(1 if accumulate else 0), stream()),
+               "air_avgpool2d_bwd")
+    return out
+
+
+def se_relu_fwd(x, z, res, out=None):
+    """out = relu(x * sigmoid(z[b, c]) + res), all dense (B, C, ...)."""
+    B, C, S = _bcs(x)
+    out = out if out is not None else torch.empty_like(x)
+    _hip.check(_hip.lib().air_se_relu_fwd(dptr(x), dptr(z), dptr(res), ci(B), ci(C), ci(S), dptr(out), stream()),
+               "air_se_relu_fwd")
+    return out
+
+
+def se_relu_bwd(x, z, out, dout, want_dres=True):
+    """Returns (dx, dz, dres or None) of se_relu_fwd."""
+    B, C, S = _bcs(x)
+    dx = torch.empty_like(x)
+    dz = torch.empty_like(z)
+    dres = torch.empty_like(x) if want_dres else None
+    _hip.check(_hip.lib().air_se_relu_bwd(dptr(x), dptr(z), dptr(out), dptr(dout), ci(B), ci(C), ci(S), dptr(dx),
+                                          dptr(dz), dptr(dres, allow_none=True), stream()), "air_se_relu_bwd")
+    return dx, dz, dres
+
+
+def log_softmax_fwd(z):
+    B, C = z.shape
+    out = torch.empty_like(z)
+    _hip.check(_hip.lib().air_log_softmax_fwd(dptr(z), ci(B), ci(C), dptr(out), stream()), "air_log_softmax_fwd")
+    return out
+
+
+def log_softmax_bwd(out, dout):
+    B, C = out.shape
+    dz = torch.empty_like(out)
+    _hip.check(_hip.lib().air_log_softmax_bwd(dptr(out), dptr(dout), ci(B), ci(C), dptr(dz), stream()),
+               "air_log_softmax_bwd")
+    return dz
 
 
 # ------------------------------------------------------------------ ECAPA (B, C, T) ops

@@ -1,7 +1,7 @@
 """Train step of the hot path (main_train.py:310-415):
 
     PCM --fused HIP LFCC (+repeat-pad/chop, transposed)--> (B,1,60,feat_len)
-        --ResNet / ECAPA / LCNN forward--> (feat, logits) --loss head--> loss
+        --ResNet / ECAPA / LCNN / Res2Net forward--> (feat, logits) --loss head--> loss
         --backward--> gradient arena --[RCCL all-reduce]--> Adam(model) + SGD(head parameter)
 
 ``Trainer`` sequences the drop-in modules exactly like the reference's loop:
@@ -314,8 +314,9 @@ class Trainer:
         one-chain capture and as the eager step: bit-identical (tests/test_dist_gpu.py)."""
         from .ecapa_tdnn import Res2Net2
         from .lcnn import LCNN
+        from .res2net import Res2Net
         from .resnet import ResNet
-        self.use_graph = bool(on) and isinstance(self.model, (Res2Net2, ResNet, LCNN))
+        self.use_graph = bool(on) and isinstance(self.model, (Res2Net2, ResNet, LCNN, Res2Net))
         if segments is None:
             env = os.environ.get("AIR_GRAPH_SEGMENTS", "")
             segments = (env == "1") if env in ("0", "1") else self.world > 1

@@ -749,6 +749,62 @@ int air_mul(const float* a, const float* b, size_t n, float* y, air_stream_t str
  * air_dropout_mask (adv_head.hip).  counter: 8-byte aligned. */
 int air_dropout_mask_ctr(float* keep, size_t n, float p, uint64_t seed, uint64_t* counter, air_stream_t stream);
 
+/* -------------------------------------------------------------- Res2Net ---
+ * model.Res2Net(SEBottle2neck, [3, 4, 6, 3], baseWidth=26, scale=4) (model.py:256-509, main_train.py:169-170).
+ * Its BatchNorms run on the BatchNorm kernels, the SE squeeze and the global average pool on air_row_stats, the SE
+ * and cls_layer Linear layers on air_linear_*, the 1x1 layers whose shape the generic kernels accept (Cin % 8 == 0,
+ * Cout % 64 == 0) on air_conv2d_*.  The kernels below are the rest. */
+/* Narrow-channel convolution (csrc/conv_narrow.hip): 3x3 pad 1 at stride 1 or 2, or 1x1 stride 1; 1 <= Cin, Cout
+ * <= 256 (AIR_EUNSUPPORTED beyond); Ho / Wo as PyTorch's.  x (B, Cin, H, W) and y (B, Cout, Ho, Wo) are NCHW with a
+ * dense (C, H, W) block and a batch stride in elements (0 = dense): channel slices of wider tensors (the Res2
+ * split / concat of model.py:459-476) are read and written in place.  The data / weight gradients take dx and dy in
+ * the same layout (x_bstride for x / dx, y_bstride for y / dy). */
+typedef struct {
+  int B, Cin, H, W, Cout, K, stride, Ho, Wo;
+  size_t x_bstride, y_bstride;
+} AirConvNarrow;
+/* y = conv(act(x), w); act = x*in_scale[ci] + in_shift[ci] (+ ReLU when relu != 0) when in_scale / in_shift are
+ * set (a BatchNorm-apply + ReLU prologue; the zero padding is not activated), identity when both are NULL. */
+int air_conv_narrow_fwd(const AirConvNarrow* p, const float* x, const float* w, const float* in_scale,
+                        const float* in_shift, int relu, float* y, air_stream_t stream);
+/* dx (=, or += when accumulate != 0) gradient with respect to the convolution's input (the activated input when the
+ * forward had a prologue). */
+int air_conv_narrow_dgrad(const AirConvNarrow* p, const float* dy, const float* w, float* dx, int accumulate,
+                          air_stream_t stream);
+/* dw (Cout, Cin, K, K) from x (with the same optional prologue as the forward) and dy.  Per-chunk partials in ws,
+ * summed in chunk order: deterministic.  ws_bytes: air_conv_narrow_wgrad_ws_bytes (0 = unsupported shape). */
+size_t air_conv_narrow_wgrad_ws_bytes(const AirConvNarrow* p);
+int air_conv_narrow_wgrad(const AirConvNarrow* p, const float* x, const float* dy, const float* in_scale,
+                          const float* in_shift, int relu, float* dw, void* ws, size_t ws_bytes, air_stream_t stream);
+/* Res2 chain step with the ReLU of model.py:466: v = relu(x*scale[c] + shift[c]) written to y1 (a channel slice of
+ * the concat); optional y2 = v + add (dense), the next branch's input "sp + spx[i+1]" (:463).  x, y1 and add are
+ * (B, C, S) with a batch stride in floats (0 = dense); add and y2 both NULL or both set.  air_res2_bn_apply
+ * (ECAPA's order, no ReLU) is unchanged. */
+int air_res2_bn_relu_apply(const float* x, size_t x_bstride, int B, int C, int S, const float* scale,
+                           const float* shift, float* y1, size_t y1_bstride, const float* add, size_t add_bstride,
+                           float* y2, air_stream_t stream);
+/* nn.AvgPool2d(k, stride, pad, ceil_mode, count_include_pad) on (B, C, H, W) channel slices (batch strides in floats,
+ * 0 = dense), PyTorch's windows and divisors: the stage block's 3x3 pool of its last split (model.py:442,
+ * count_include_pad) and the downsample's 2x2 ceil-mode pool (:294-298, count_include_pad=False).  Ho / Wo must be
+ * PyTorch's output size.  The backward gathers each input's windows in the order PyTorch adds them; accumulate != 0
+ * adds to dx. */
+int air_avgpool2d_fwd(const float* x, size_t x_bstride, int B, int C, int H, int W, int k, int stride, int pad,
+                      int ceil_mode, int count_include_pad, int Ho, int Wo, float* y, size_t y_bstride,
+                      air_stream_t stream);
+int air_avgpool2d_bwd(const float* dy, size_t dy_bstride, int B, int C, int H, int W, int k, int stride, int pad,
+                      int ceil_mode, int count_include_pad, int Ho, int Wo, float* dx, size_t dx_bstride,
+                      int accumulate, air_stream_t stream);
+/* SE tail of a block (model.py:480-487, :504-505): out = relu(x*sigmoid(z[b][c]) + res), all (B, C, S) dense.
+ * bwd: with dpre = dout where out > 0: dx = dpre*sigmoid(z), dres = dpre (NULL: not written), dz[b][c] =
+ * sigmoid'(z) sum_s dpre*x (one workgroup per row, fixed order).  air_se_scale_* (ECAPA, no ReLU) is unchanged. */
+int air_se_relu_fwd(const float* x, const float* z, const float* res, int B, int C, int S, float* out,
+                    air_stream_t stream);
+int air_se_relu_bwd(const float* x, const float* z, const float* out, const float* dout, int B, int C, int S,
+                    float* dx, float* dz, float* dres, air_stream_t stream);
+/* F.log_softmax(z, dim=-1) of the (B, C) logits (model.py:353) and its backward dz = dout - exp(out) sum_c dout. */
+int air_log_softmax_fwd(const float* z, int B, int C, float* out, air_stream_t stream);
+int air_log_softmax_bwd(const float* out, const float* dout, int B, int C, float* dz, air_stream_t stream);
+
 /* ----------------------------------------------------------- OC-Softmax ---
  * AngularIsoLoss.forward == OCSoftmax.forward (loss.py:73-97, :187-206).
  * x (B,D), center (1,D), labels (B,) int64.  loss: scalar; neg_scores (B,).

@@ -43,6 +43,18 @@ def lib_path():
     return _LIB_PATH
 
 
+def _freeze_in_forked_child():
+    """A process forked from one that uses the GPU (a DataLoader worker, a multiprocessing manager) inherits the parent's
+    garbage: tensors in pinned memory, events, captured graphs.  It cannot use the GPU, and the collector running their
+    destructors there calls into a runtime the fork did not carry over.  gc.freeze() keeps everything allocated before
+    the fork out of the child's collections (the parent still frees it); what the child allocates is collected as usual."""
+    import gc
+    gc.freeze()
+
+
+_fork_hook = False
+
+
 def lib():
     """Load libair_hip.so once.  Raises HipExtensionMissing (never falls back)."""
     global _lib
@@ -51,7 +63,11 @@ def lib():
             raise HipExtensionMissing(
                 "HIP extension not built: %s is missing. Run `python -m asvspoof2021_air_amd.build` "
                 "(or __graft_entry__.build()). There is no CPU fallback." % _LIB_PATH)
+        global _fork_hook
         _lib = ctypes.CDLL(_LIB_PATH)
+        if not _fork_hook and hasattr(os, "register_at_fork"):
+            os.register_at_fork(after_in_child=_freeze_in_forked_child)
+            _fork_hook = True
         _lib.air_version.restype = ctypes.c_char_p
         _lib.air_option_name.restype = ctypes.c_char_p
         _lib.air_lfcc_plan_bytes.restype = ctypes.c_size_t

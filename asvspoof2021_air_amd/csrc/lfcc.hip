@@ -85,6 +85,16 @@ struct LfccArgs {
   const float* silence;  // padded mode, AIR_PAD_SILENCE: the D-float frame to prepend (dataset.py:13-16)
   int L, T, tiles, flags, feat_len, pad_mode;
 };
+// Ragged batches (air_lfcc_fwd_ragged): L is the row capacity Lcap, T / tiles those of a full row, and every row
+// carries its own length.  A struct of its own, so that lfcc_kernel's kernel arguments stay what they were.
+struct LfccRaggedArgs : LfccArgs {
+  const int* lengths;  // (B,) samples of each row, clamped to [1, L] on the device
+};
+// (A/B knob: -DLFCC_RAGGED_NOSKIP=1 lets the dead tiles of a ragged row stage and compute like live ones - what the
+// early exit is worth, profiles/ragged_lfcc.md)
+#ifndef LFCC_RAGGED_NOSKIP
+#define LFCC_RAGGED_NOSKIP 0
+#endif
 
 constexpr int FLAG_EMPH = AIR_LFCC_EMPHASIS;
 constexpr int FLAG_DELTA = AIR_LFCC_DELTA;
@@ -97,8 +107,11 @@ constexpr int FLAG_PADDED = 1 << 8;  // internal: (B, D, feat_len) output
 // 20): 20 filters, 26 bins) - the filterbank and DCT loops unroll onto immediate LDS offsets with no index arithmetic
 // (round 5: the kernel is VALU-issue bound - SQ_ACTIVE_INST_VALU 59 % of its cycles, 1314 VALU instructions per wave,
 // profiles/r05_lfcc.md - and ~40 % of them were address arithmetic, clamps and the correctly rounded sqrt).  0: any plan.
-template <int NF_C, int MW_C>
-__device__ __forceinline__ void lfcc_body(const LfccArgs& a, float* __restrict__ s_pcm, float* __restrict__ s_xch,
+// RAGGED (Args = LfccRaggedArgs, padded layout only): the row's own L and T come from a.lengths[b]; a workgroup whose
+// tile holds no frame the row writes leaves before it stages anything.  Every tile computes its own halo, so the tiles
+// that stay write what they would have written.  The fixed-length instantiation compiles to the code it always had.
+template <int NF_C, int MW_C, bool RAGGED = false, class Args = LfccArgs>
+__device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_pcm, float* __restrict__ s_xch,
                                           float* __restrict__ s_c, float* __restrict__ s_fbwT,
                                           float* __restrict__ s_dctT) {
   const int tid = threadIdx.x;
@@ -110,9 +123,23 @@ __device__ __forceinline__ void lfcc_body(const LfccArgs& a, float* __restrict__
   const LfccPlan* __restrict__ plan = a.plan;
   const int nfilt = NF_C ? NF_C : plan->nfilt;
   const int maxw = MW_C ? MW_C : plan->maxw;
-  const int L = a.L, T = a.T;
-  const float* __restrict__ row = a.pcm + (size_t)b * L;
-  const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * L : nullptr;
+  int L = a.L, T = a.T;
+  int live_tiles = a.tiles;  // tiles of this row that write frames: they share the row's constant frames
+  bool dead = false;         // ragged: this tile holds no frame that the row writes
+  if constexpr (RAGGED) {
+    L = min(max(a.lengths[b], 1), a.L);  // a bad length in device memory must not read outside the row
+    T = 1 + L / FS;
+    live_tiles = (T + FOUT - 1) / FOUT;
+    dead = t0 >= T;
+    if (T > a.feat_len) {
+      // chopped row: only the tiles that overlap [start, start + feat_len) are written (same clamp as below)
+      const int st = a.start != nullptr ? min(max(a.start[b], 0), T - a.feat_len) : 0;
+      dead = dead || t0 + FOUT <= st || t0 >= st + a.feat_len;
+    }
+    if (!LFCC_RAGGED_NOSKIP && dead) return;  // (workgroup-uniform, ahead of every barrier)
+  }
+  const float* __restrict__ row = a.pcm + (size_t)b * a.L;
+  const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * a.L : nullptr;
   // sample m of this utterance as the float the reference's loader hands to LFCC.forward
   auto sample = [&](long m) -> float { return row16 ? (float)row16[m] * (1.0f / 32768.0f) : row[m]; };
 
@@ -302,6 +329,7 @@ __device__ __forceinline__ void lfcc_body(const LfccArgs& a, float* __restrict__
     air_wave_lds_fence();  // next group overwrites the exchange tile
   }
   __syncthreads();
+  if (RAGGED && LFCC_RAGGED_NOSKIP && dead) return;  // (A/B only: staged and computed, nothing to write)
 
   // ---- deltas into an LDS tile, then coalesced stores -----------------------
   // Round 5: a thread takes one coefficient of TWO neighbouring frames - six clamped cepstra c(t-2) .. c(t+3) give the
@@ -310,7 +338,7 @@ __device__ __forceinline__ void lfcc_body(const LfccArgs& a, float* __restrict__
   const bool with_delta = (a.flags & FLAG_DELTA) != 0;
   const int D = with_delta ? 3 * nfilt : nfilt;
   const int base = t0 - HALO;  // global frame of local row 0
-  const bool padded = (a.flags & FLAG_PADDED) != 0;
+  const bool padded = RAGGED || (a.flags & FLAG_PADDED) != 0;
   constexpr int OSTR = FOUT + 1;  // padded layout: s_out[c][fo], odd stride (conflict-free along fo)
   float* __restrict__ s_out = s_xch;
   {
@@ -384,7 +412,7 @@ __device__ __forceinline__ void lfcc_body(const LfccArgs& a, float* __restrict__
       // the npad constant frames (zeros appended, :513-517, or the silence frame prepended, :524-528),
       // shared out over the utterance's tiles
       const int lo = a.pad_mode == AIR_PAD_SILENCE ? 0 : T;
-      for (int e = tile * NTHREADS + tid; e < npad * D; e += a.tiles * NTHREADS) {
+      for (int e = tile * NTHREADS + tid; e < npad * D; e += live_tiles * NTHREADS) {
         const int c = e / npad, k = e - c * npad;
         obase[(size_t)c * flen + lo + k] = a.pad_mode == AIR_PAD_SILENCE ? a.silence[c] : 0.0f;
       }
@@ -403,6 +431,18 @@ __global__ __launch_bounds__(NTHREADS, LFCC_MINB) void lfcc_kernel(LfccArgs a) {
     lfcc_body<20, 26>(a, s_pcm, s_xch, s_c, s_fbwT, s_dctT);
   else
     lfcc_body<0, 0>(a, s_pcm, s_xch, s_c, s_fbwT, s_dctT);
+}
+
+__global__ __launch_bounds__(NTHREADS, LFCC_MINB) void lfcc_ragged_kernel(LfccRaggedArgs a) {
+  __shared__ __attribute__((aligned(16))) float s_pcm[NSAMP];
+  __shared__ __attribute__((aligned(16))) float s_xch[NW * XCH_FLOATS];
+  __shared__ float s_c[FCOMP * MAXF];
+  __shared__ float s_fbwT[MAXW * MAXF];
+  __shared__ float s_dctT[MAXF * MAXF];
+  if (a.plan->pad0 == 1)
+    lfcc_body<20, 26, true>(a, s_pcm, s_xch, s_c, s_fbwT, s_dctT);
+  else
+    lfcc_body<0, 0, true>(a, s_pcm, s_xch, s_c, s_fbwT, s_dctT);
 }
 
 // ---- in-place pre-emphasis (the reference mutates its input, :106) ----------
@@ -491,6 +531,41 @@ int lfcc_launch(const float* pcm, const short* pcm16, int B, int L, float* out, 
   return AIR_OK;
 }
 
+// Ragged batch: B rows of capacity Lcap, row b holding lengths[b] samples.  The grid covers a full row for every
+// utterance (B x ceil(Tcap / FOUT)); what a shorter row does not need leaves at once (lfcc_body).
+int lfcc_launch_ragged(const float* pcm, const short* pcm16, int B, int Lcap, const int* lengths, float* out,
+                       int feat_len, const int* start, const void* plan_dev, int flags, hipStream_t stream, int pad_mode,
+                       const float* silence) {
+  if ((pcm != nullptr) == (pcm16 != nullptr) || !lengths || !out || !plan_dev || B <= 0 || Lcap <= 0 || feat_len <= 0)
+    return AIR_EINVAL;
+  if (pad_mode < AIR_PAD_REPEAT || pad_mode > AIR_PAD_SILENCE) return AIR_EINVAL;
+  if (pad_mode == AIR_PAD_SILENCE && !silence) return AIR_EINVAL;
+  const int Tcap = 1 + Lcap / FS;
+  LfccRaggedArgs a;
+  a.pcm = pcm;
+  a.pcm16 = pcm16;
+  a.out = out;
+  a.plan = reinterpret_cast<const LfccPlan*>(plan_dev);
+  a.start = start;
+  a.silence = silence;
+  a.pad_mode = pad_mode;
+  a.L = Lcap;
+  a.T = Tcap;
+  a.tiles = (Tcap + FOUT - 1) / FOUT;
+  a.flags = flags | FLAG_PADDED;
+  a.feat_len = feat_len;
+  a.lengths = lengths;
+  {
+    // algorithmic bytes: the lengths live on the device, so the input is accounted at the row capacity Lcap (an upper
+    // bound on what the live tiles read) + the fp32 features out
+    const int nf = (flags & FLAG_DELTA) ? 3 : 1;
+    AirProfScope ps(AIR_K_LFCC, B * ((pcm16 ? 2.0 : 4.0) * Lcap + 4.0 * (double)feat_len * nf * 20.0), stream);
+    hipLaunchKernelGGL(lfcc_ragged_kernel, dim3((unsigned)(B * a.tiles)), dim3(NTHREADS), 0, stream, a);
+  }
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -574,6 +649,14 @@ int air_lfcc_fwd_padded_ex(const float* pcm, const int16_t* pcm16, int B, int L,
   return lfcc_launch(pcm, reinterpret_cast<const short*>(pcm16), B, L, out, feat_len, start_dev, plan_dev,
                      (flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA)) | FLAG_PADDED, air_stream(stream), pad_mode,
                      silence_dev);
+}
+
+int air_lfcc_fwd_ragged(const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev, float* out,
+                        int feat_len, const int* start_dev, const void* plan_dev, int flags, int pad_mode,
+                        const float* silence_dev, air_stream_t stream) {
+  return lfcc_launch_ragged(pcm, reinterpret_cast<const short*>(pcm16), B, Lcap, lengths_dev, out, feat_len, start_dev,
+                            plan_dev, flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA), air_stream(stream), pad_mode,
+                            silence_dev);
 }
 
 int air_lfcc_fwd_padded_i16(const int16_t* pcm16, int B, int L, float* out, int feat_len,

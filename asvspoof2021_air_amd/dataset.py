@@ -10,7 +10,9 @@
   * raw PCM (``PCMSource``: any list of waveforms; ``SyntheticSource``: the separable synthetic corpus of synth.py),
     whose features come from the fused HIP LFCC (+ pad / chop) kernel instead of a ``.pt`` file.  Per item that is a
     batch-1 launch (what preprocess.py:239-244 does); with ``return_pcm=True`` the item carries the waveform and
-    ``collate_fn`` runs ONE fused LFCC -> pad/chop launch for the batch.
+    ``collate_fn`` runs ONE fused LFCC -> pad/chop launch for the batch.  ``return_pcm='batch'`` / ``'ragged'`` hand the
+    waveforms themselves to the trainer as one pinned host tensor (one length per batch / any lengths + ``lengths`` and
+    crop offsets), whose fused front-end makes the features inside the replayed step.
 
 Class names, constructor arguments, ``tag`` / ``label`` / ``channel`` maps, the pad / chop semantics and the
 ``np.random.randint(T - feat_len)`` crop draw (dataset.py:69: the last valid offset is never drawn) are the
@@ -230,7 +232,10 @@ class _SpoofDataset(Dataset):
     def _init_common(self, feature, feat_len, pad_chop, padding, return_pcm):
         self.feat_len, self.feature, self.pad_chop, self.padding = feat_len, feature, pad_chop, padding
         self.label = dict(LABEL)
-        self.return_pcm = "batch" if return_pcm == "batch" else bool(return_pcm)
+        self.return_pcm = return_pcm if return_pcm in ("batch", "ragged") else bool(return_pcm)
+        # return_pcm='ragged': samples per row of the batch tensor (Lcap).  None: the batch's longest utterance rounded up
+        # to a multiple of 16000 - every new capacity re-captures a replayed step, so give a fixed one for training
+        self.ragged_samples = None
         self._lfcc = None
         self._silence_cpu = None
         if padding == "silence" and pad_chop and torch.cuda.is_available():
@@ -350,7 +355,7 @@ class _SpoofDataset(Dataset):
             ev.synchronize()
             slot["events"][j] = None
         buf = slot["bufs"][j]
-        buf._air_ring = (slot, j)
+        buf._air_ring = (slot["events"], j)  # (the events list, not the slot: the slot holds the buffer - no reference cycle)
         return buf
 
     def collate_fn(self, samples):
@@ -380,6 +385,8 @@ class _SpoofDataset(Dataset):
                 else:
                     pcm[j].copy_(w)
             return [pcm] + default_collate([smp[1:] for smp in samples])
+        if self.return_pcm == "ragged":
+            return self._collate_ragged(samples)
         if not self.pad_chop:
             raise ValueError("return_pcm needs pad_chop=True (one feat_len per batch)")
         next(s for s in self._sources() if isinstance(s, PCMSource))._need_gpu_here("collate_fn(return_pcm=True)")
@@ -408,6 +415,47 @@ class _SpoofDataset(Dataset):
                 out[torch.tensor(js, device=dev)] = got
         rest = default_collate([tuple(s[1:]) for s in samples])
         return [out.unsqueeze(1).transpose(2, 3)] + list(rest)
+
+
+    RAGGED_ROUND = 16000  # ragged_samples None: the capacity is the longest utterance rounded up to this
+
+    def _collate_ragged(self, samples):
+        """``return_pcm='ragged'``: utterances of ANY length as one pinned (B, Lcap) host tensor (tails zero-filled) + int32
+        ``lengths`` (B,) + int32 ``start`` (B,) + the collated meta.  ``start`` holds the crop offsets of dataset.py:69, drawn
+        in item order, one ``np.random.randint(T_b - feat_len)`` per utterance longer than feat_len (0 otherwise) - the
+        draws the ``return_pcm=True`` path makes.  Trainer.step(pcm, labels, start=start, lengths=lengths) makes the
+        features in ONE launch inside the replayed hipGraph (LFCC.forward_ragged)."""
+        dtype = samples[0][0].dtype
+        if dtype not in (torch.float32, torch.int16) or any(smp[0].dtype != dtype for smp in samples):
+            raise ValueError("return_pcm='ragged' needs utterances of one dtype per batch, float32 or int16 (got %s)" % sorted(
+                set(str(smp[0].dtype) for smp in samples)))
+        lens = [int(smp[0].shape[0]) for smp in samples]
+        cap = self.ragged_samples
+        if cap is None:
+            cap = -(-max(lens) // self.RAGGED_ROUND) * self.RAGGED_ROUND
+        else:
+            cap = int(cap)
+            for smp, n in zip(samples, lens):
+                if n > cap:
+                    raise ValueError("%s has %d samples, more than ragged_samples = %d" % (smp[1], n, cap))
+        if min(lens) < 1:
+            raise ValueError("return_pcm='ragged' needs at least one sample per utterance")
+        pcm = self._pinned_batch(len(samples), cap, dtype)
+        dst = pcm.numpy()  # rows through numpy, one memcpy each (see 'batch' above)
+        for j, (smp, n) in enumerate(zip(samples, lens)):
+            w = smp[0]
+            if w.device.type == "cpu" and w.is_contiguous():
+                dst[j, :n] = w.numpy()
+            else:
+                pcm[j, :n].copy_(w)
+            dst[j, n:] = 0
+        start = np.zeros(len(samples), dtype=np.int32)
+        for j, n in enumerate(lens):
+            T = 1 + n // self.lfcc.fs
+            if T > self.feat_len:
+                start[j] = np.random.randint(T - self.feat_len)
+        return [pcm, torch.tensor(lens, dtype=torch.int32), torch.from_numpy(start)] + default_collate(
+            [smp[1:] for smp in samples])
 
 
 class ASVspoof2019(_SpoofDataset):
@@ -597,7 +645,7 @@ class DevicePrefetcher:
             for x in batch:  # a ring-buffer batch (collate_fn, return_pcm='batch'): its slot is reusable after this copy
                 ring = getattr(x, "_air_ring", None) if torch.is_tensor(x) else None
                 if ring is not None:
-                    ring[0]["events"][ring[1]] = ev
+                    ring[0][ring[1]] = ev
             queue.append((moved, ev, slot))
             return True
 

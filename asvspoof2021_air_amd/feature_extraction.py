@@ -188,6 +188,44 @@ class LFCC(nn.Module):
                    "air_lfcc_fwd_padded_ex")
         return out
 
+    def forward_ragged(self, x, lengths, feat_len=750, start=None, padding="repeat"):
+        """A batch of utterances of DIFFERENT lengths in one launch: ``x`` (B, Lcap) float32 or int16 on the GPU, row b
+        holding ``lengths[b]`` samples (what follows them is never read) -> (B, out_dim, feat_len), row b being what
+        ``forward_padded`` gives for that utterance alone.  Does not mutate ``x``.  ``lengths``: int32 (B,); a GPU tensor is
+        used as is (the kernel clamps it to [1, Lcap]), a host tensor or list is checked (ValueError) and uploaded.
+        ``start`` / ``padding``: as in ``forward_padded``, each row's offset clamped to its own [0, T_b - feat_len]."""
+        self._check(x)
+        mode = pad_mode_id(padding)
+        B, Lcap = x.shape
+        if not (torch.is_tensor(lengths) and lengths.is_cuda):
+            host = torch.as_tensor(lengths).reshape(-1)
+            if host.numel() != B or host.is_floating_point():
+                raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
+            if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
+                raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
+                    Lcap, int(host.min()), int(host.max())))
+            lengths = host.to(torch.int32).to(x.device)
+        elif lengths.numel() != B:
+            raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
+        lengths = lengths.to(torch.int32).contiguous()  # (no-op for what the dataset hands over)
+        if start is not None and not (torch.is_tensor(start) and start.is_cuda):
+            start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
+        i16 = x.dtype == torch.int16
+        src = x.contiguous() if i16 else (x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous())
+        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
+        sil = self.silence_row(x.device) if mode == 2 else None
+        lib = _hip.lib()
+        null = _hip.dptr(None, allow_none=True)
+        _hip.check(lib.air_lfcc_fwd_ragged(null if i16 else _hip.dptr(src),
+                                           _hip.dptr(src, torch.int16) if i16 else null,
+                                           _hip.ci(B), _hip.ci(Lcap), _hip.dptr(lengths, torch.int32), _hip.dptr(out),
+                                           _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
+                                           _hip.dptr(self.plan(x.device), torch.uint8),
+                                           _hip.ci(self._flags()), _hip.ci(mode), _hip.dptr(sil, allow_none=True),
+                                           _hip.stream()),
+                   "air_lfcc_fwd_ragged")
+        return out
+
     def _forward_i16(self, x, feat_len, start):
         """16-bit PCM straight from the wav/flac samples (x = s / 32768 inside the kernel: the floats
         soundfile / librosa hand the reference), in either layout (feat_len 0 = (B, T, D))."""

@@ -130,11 +130,15 @@ def test_on_dataset(model, loader, score_file, loss_model=None, add_loss=None, t
 
 
 @torch.no_grad()
-def score_pcm(model, loss_model, pcm, feat_len=750, ecapa=False, add_loss="ocsoftmax", lfcc=None):
-    """(B, L) raw PCM on the GPU -> (B,) scores as written to the file (``-score``)."""
+def score_pcm(model, loss_model, pcm, feat_len=750, ecapa=False, add_loss="ocsoftmax", lfcc=None, lengths=None, start=None):
+    """(B, L) raw PCM on the GPU -> (B,) scores as written to the file (``-score``).  ``lengths``: int32 (B,), a ragged
+    batch - row b holds lengths[b] samples (LFCC.forward_ragged); ``start``: optional int32 (B,) crop offsets."""
     if lfcc is None:
         lfcc = LFCC(320, 160, 512, 16000, 20, with_energy=False).to(pcm.device)
         lfcc.mutate_input = False
-    feat = lfcc.forward_padded(pcm, feat_len, None)
+    if lengths is not None:
+        feat = lfcc.forward_ragged(pcm, lengths, feat_len, start)
+    else:
+        feat = lfcc.forward_padded(pcm, feat_len, start)
     model.eval()
     return -batch_scores(model, feat if ecapa else feat.unsqueeze(1), loss_model, add_loss)

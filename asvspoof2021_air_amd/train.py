@@ -222,9 +222,16 @@ class Trainer:
         if self.loss_optimizer is not None and self.add_loss != "iso_sq":
             adjust_learning_rate(self.lr0, self.loss_optimizer, epoch_num, lr_decay, interval)
 
-    def features(self, pcm, start=None):
-        """(B, L) PCM -> model input, fused on the GPU (dataset.py:66-79 + main_train.py:338,:347)."""
-        feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, 60, feat_len)
+    def features(self, pcm, start=None, lengths=None):
+        """(B, L) PCM -> model input, fused on the GPU (dataset.py:66-79 + main_train.py:338,:347).  ``lengths``: int32
+        (B,), the batch is ragged - row b of ``pcm`` holds lengths[b] samples (LFCC.forward_ragged)."""
+        if lengths is not None:
+            if self.augment is not None:
+                # the IR convolution normalises over the whole row: a ragged row would be scaled by its padding
+                raise NotImplementedError("ragged batches (lengths=...) are not supported together with augment")
+            feat = self.lfcc.forward_ragged(pcm, lengths, self.feat_len, start, self.padding)
+        else:
+            feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, 60, feat_len)
         return feat if self.ecapa else feat.unsqueeze(1)
 
     def _head(self, feats, logits, labels):
@@ -268,13 +275,13 @@ class Trainer:
         return loss.detach(), second
 
     @torch.no_grad()
-    def eval_batch(self, pcm, labels, start=None):
+    def eval_batch(self, pcm, labels, start=None, lengths=None):
         """The dev pass of main_train.py:526-575 for one batch: (loss, score) with the reference's score of each head -
         softmax(logits)[:, 0] (None), |feats - center| (isolate / iso_sq), the head's second output (ang_iso, p2sgrad).
         Eval-mode model; feeds ``save_checkpoint(val_loss=...)`` for any head."""
         from . import ops
         self.model.eval()
-        feats, logits = self.model(self.features(pcm, start))
+        feats, logits = self.model(self.features(pcm, start, lengths))
         labels = labels.to(device=feats.device, dtype=torch.int64).contiguous()
         if self.add_loss is None:
             return self.ce(logits, labels), ops.softmax_rows(logits)[:, 0]
@@ -284,14 +291,19 @@ class Trainer:
                                    float(lm.r_fake), self.add_loss == "iso_sq", want_dist=True)
         return self.loss(feats, labels)
 
-    def step(self, pcm, labels, start=None):
+    def step(self, pcm, labels, start=None, lengths=None):
+        """``lengths`` None: a batch of one length; a ``start`` forces the eager step.  ``lengths`` int32 (B,): a ragged
+        batch - the crop offsets and the lengths are device data of the captured step, so it stays on hipGraph replay
+        with or without ``start``, and every batch of one (B, Lcap) shape replays the same capture."""
+        if lengths is not None and self.augment is not None:
+            raise NotImplementedError("ragged batches (lengths=...) are not supported together with augment")
         if self.augment is not None:
             pcm = self.augment(pcm)
-        if self.use_graph and start is None:
-            out = self._graphed_step(pcm, labels)
+        if self.use_graph and (start is None or lengths is not None):
+            out = self._graphed_step(pcm, labels, lengths, start)
             if out is not None:
                 return out
-        return self.step_features(self.features(pcm, start), labels)
+        return self.step_features(self.features(pcm, start, lengths), labels)
 
     # ------------------------------------------------------------------ hipGraph replay
     def enable_graph(self, on=True, segments=None):
@@ -351,18 +363,23 @@ class Trainer:
             return ("p2sgrad", float(self.loss.smooth))
         return ("ce",)
 
-    def _graph_key(self, pcm, labels):
+    def _graph_key(self, pcm, labels, ragged=False):
         """Everything a capture freezes: shapes, the arithmetic mode and the scalars that travel as kernel
-        arguments (loss weight and the head's own: OC-Softmax margins / scale, Isolate radii, P2SGrad smoothing)."""
+        arguments (loss weight and the head's own: OC-Softmax margins / scale, Isolate radii, P2SGrad smoothing).
+        ``ragged``: the capture holds the ragged front-end (lengths and crop offsets are its device inputs, not its key)."""
         return (tuple(pcm.shape), pcm.dtype, tuple(labels.shape), getattr(self.model, "compute_dtype", "fp32"),
                 self.feat_len, float(self.weight_loss)) + self._head_scalars() + (
-                self.padding, getattr(self.model, "noise_mode", None), getattr(self.model, "noise_scale", None))
+                self.padding, getattr(self.model, "noise_mode", None), getattr(self.model, "noise_scale", None)) + (
+                ("ragged",) if ragged else ())
 
-    def _graphed_step(self, pcm, labels):
+    def _graphed_step(self, pcm, labels, lengths=None, start=None):
         from . import ops
         if getattr(self.model, "noise_mode", None) == "tensor":
             return None  # an installed noise tensor (parity tests) is host state: eager
-        key = self._graph_key(pcm, labels)
+        ragged = lengths is not None
+        if ragged:
+            lengths = self._ragged_lengths(lengths, pcm)
+        key = self._graph_key(pcm, labels, ragged)
         g = self._graph
         if g is not None and (g["key"] != key or g["ws_gen"] != ops.workspace_generation()):
             # another shape / hyper-parameter, or an eager step in between outgrew a scratch buffer the graph
@@ -374,7 +391,7 @@ class Trainer:
             if self._graph_warm < 2:
                 self._graph_warm += 1
                 return None
-            g = self._capture_or_fall_back(key, pcm, labels)
+            g = self._capture_or_fall_back(key, pcm, labels, lengths, start)
             if g is None:
                 return None  # (every rank alike: the eager step takes over)
         if not self.model.training:  # an interleaved score() left eval mode behind
@@ -387,6 +404,12 @@ class Trainer:
                 p.grad = gr
         g["pcm"].copy_(pcm, non_blocking=True)
         g["labels"].copy_(labels, non_blocking=True)
+        if ragged:
+            g["lengths"].copy_(lengths, non_blocking=True)
+            if start is None:
+                g["start"].zero_()
+            else:
+                g["start"].copy_(torch.as_tensor(start), non_blocking=True)
         # graph k's replay, then (world > 1, segments) the all-reduce of the arena slice it completed - launched on the
         # communication stream behind an event, so that the next replay is enqueued right away
         bucketer = None
@@ -415,16 +438,28 @@ class Trainer:
         self._optimise(scale)
         return g["loss"].detach().clone(), (g["neg"].clone() if g["neg"] is not None else None)
 
-    def _capture_or_fall_back(self, key, pcm, labels):
+    def _ragged_lengths(self, lengths, pcm):
+        """``lengths`` as the int32 (B,) device tensor a replay copies into the capture's buffer; host values are checked
+        like LFCC.forward_ragged checks them."""
+        if not (torch.is_tensor(lengths) and lengths.is_cuda):
+            host = torch.as_tensor(lengths).reshape(-1)
+            if host.numel() != pcm.shape[0] or host.is_floating_point() or int(host.min()) < 1 or int(host.max()) > pcm.shape[1]:
+                raise ValueError("lengths must be %d integers in [1, %d]" % (pcm.shape[0], pcm.shape[1]))
+            lengths = host.to(torch.int32).to(pcm.device, non_blocking=True)
+        if lengths.numel() != pcm.shape[0]:
+            raise ValueError("lengths must have %d entries, got %d" % (pcm.shape[0], lengths.numel()))
+        return lengths
+
+    def _capture_or_fall_back(self, key, pcm, labels, lengths=None, start=None):
         """The capture, guarded for world > 1: were it to fail on ANY rank (a runtime that refuses a call inside a
         capture, memory), EVERY rank drops the graph and goes on with the eager bucketed step - one rank replaying
         while another launches its all-reduces from inside backward would pair the wrong collectives.  The agreement
         costs one 4-byte all-reduce at capture time.  world 1: errors propagate as before."""
         if self.world == 1:
-            return self._capture(key, pcm, labels)
+            return self._capture(key, pcm, labels, lengths, start)
         err = None
         try:
-            g = self._capture(key, pcm, labels)
+            g = self._capture(key, pcm, labels, lengths, start)
         except Exception as exc:  # noqa: BLE001
             g, err = None, exc
         dev = self.device if td.get_backend() == "nccl" else "cpu"
@@ -439,11 +474,11 @@ class Trainer:
         self.enable_graph(False)  # restores the side stream and the in-backward bucketer
         return None
 
-    def _fwd_bwd_direct(self, pcm, labels):
+    def _fwd_bwd_direct(self, pcm, labels, lengths=None, start=None):
         """front-end + forward + loss + backward as plain calls in THIS thread (what model(x) -> loss.backward() does
         through autograd, whose backward runs on a worker thread): (loss, second output, [(param, grad)])."""
         model = self.model
-        feats, saved = model.forward_saved(self.features(pcm, None))
+        feats, saved = model.forward_saved(self.features(pcm, start, lengths))
         if self.add_loss is None:  # the CE head: the gradient enters through the logits (fc_mu / fc7, bn7)
             leaf = saved["logits"].detach().requires_grad_(True)
             loss, bwd, second = self._head(None, leaf, labels)
@@ -462,12 +497,19 @@ class Trainer:
         pairs += [(p, p.grad) for p in self._loss_params() if p.grad is not None]
         return loss, second, pairs
 
-    def _capture(self, key, pcm, labels):
+    def _capture(self, key, pcm, labels, lengths=None, start=None):
         """The step recorded through _fwd_bwd_direct on a capture stream: one hipGraph, or (graph_segments) several sharing
-        one memory pool, cut at backward's bucket boundaries (enable_graph)."""
+        one memory pool, cut at backward's bucket boundaries (enable_graph).  A ragged capture (``lengths``) owns static
+        int32 ``lengths`` and ``start`` buffers beside ``pcm`` and ``labels``; every replay refreshes them."""
         from . import ops
         self.model.train()
         s_pcm, s_labels = pcm.detach().clone(), labels.detach().clone()
+        s_len = s_start = None
+        if lengths is not None:
+            s_len = lengths.detach().to(torch.int32).clone()
+            s_start = torch.zeros(pcm.shape[0], dtype=torch.int32, device=pcm.device)
+            if start is not None:
+                s_start.copy_(torch.as_tensor(start))
         self._zero_grads()
         arena = self.model.arena()
         pool = torch.cuda.graph_pool_handle()
@@ -503,7 +545,7 @@ class Trainer:
             with torch.cuda.stream(cap):
                 begin()
                 try:
-                    loss, neg, grads = self._fwd_bwd_direct(s_pcm, s_labels)
+                    loss, neg, grads = self._fwd_bwd_direct(s_pcm, s_labels, s_len, s_start)
                 except BaseException:
                     try:  # leave the stream out of capture mode: the caller may go on eagerly (_capture_or_fall_back)
                         state["g"].capture_end()
@@ -522,14 +564,15 @@ class Trainer:
         # p.grad now ARE the tensors the captured kernels write (no zero_grad between replays - every gradient is
         # overwritten, none accumulated); kept in "grads" so _graphed_step can restore them after eager interludes
         self._graph = dict(key=key, graphs=graphs, segments=graphs if self.graph_segments else None, pool=pool, pcm=s_pcm,
-                           labels=s_labels, loss=loss, neg=neg, grads=grads, ws_gen=ops.workspace_generation())
+                           labels=s_labels, lengths=s_len, start=s_start, loss=loss, neg=neg, grads=grads,
+                           ws_gen=ops.workspace_generation())
         return self._graph
 
     @torch.no_grad()
-    def score(self, pcm, start=None):
+    def score(self, pcm, start=None, lengths=None):
         """generate_score.py:91-110: the value written to the score file (+cos similarity for ang_iso and p2sgrad,
         softmax(logits)[:, 0] for the CE head - and for isolate / iso_sq, which generate_score.py has no branch for)."""
         from .generate_score import batch_scores
         self.model.eval()
         add = {"ang_iso": "ocsoftmax", "p2sgrad": "p2sgrad"}.get(self.add_loss)
-        return -batch_scores(self.model, self.features(pcm, start), self.loss, add)
+        return -batch_scores(self.model, self.features(pcm, start, lengths), self.loss, add)

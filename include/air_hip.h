@@ -122,6 +122,15 @@ int air_lfcc_fwd_padded(const float* pcm, int B, int L, float* out, int feat_len
 int air_lfcc_fwd_padded_ex(const float* pcm, const int16_t* pcm16, int B, int L, float* out, int feat_len,
                            const int* start_dev, const void* plan_dev, int flags, int pad_mode,
                            const float* silence_dev, air_stream_t stream);
+/* Ragged batch: B rows of capacity Lcap (row b = pcm + b * Lcap), of which the first lengths_dev[b] samples are the
+ * utterance.  Row b of out, (B, D, feat_len), is exactly what air_lfcc_fwd_padded_ex writes for that utterance alone
+ * with L = L_b = clamp(lengths_dev[b], 1, Lcap) (the clamp only keeps a bad device value inside its row): same crop
+ * clamp, pad modes and deltas clamped at the utterance's own ends.  No sample at index >= L_b is read.  One launch of
+ * B x ceil((1 + Lcap/fs) / 28) workgroups; those a row does not need return at once.  Exactly one of pcm / pcm16 is
+ * non-NULL; feat_len <= 0, a NULL lengths_dev or a bad pad_mode: AIR_EINVAL. */
+int air_lfcc_fwd_ragged(const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev, float* out,
+                        int feat_len, const int* start_dev, const void* plan_dev, int flags, int pad_mode,
+                        const float* silence_dev, air_stream_t stream);
 /* Same from 16-bit PCM as stored in the corpus' wav/flac files: the kernel converts s -> s / 32768 (exact, what
  * soundfile/librosa hand the reference, preprocess.py:239-241), so the features are bit-identical to the fp32
  * entry points on the converted samples while the kernel reads half the bytes (128 KB instead of 256 KB per

@@ -21,6 +21,7 @@ class ParamArena:
         SURVEY.md §3b)."""
         head = [(n, p) for n, p in named_params if n not in tail_names]
         tail = [(n, p) for n, p in named_params if n in tail_names]
+        self.tail_names = tuple(tail_names)
         self.entries = []  # (name, param, offset, numel)
         off = 0
         for n, p in head + tail:

@@ -33,7 +33,7 @@ import torch.nn as nn
 
 from . import _hip, ops
 from . import ops_h as oh
-from .arena import ParamArena
+from .hip_model import HipModel
 from .schedule import BackwardSchedule
 
 
@@ -60,7 +60,7 @@ class SEModule(nn.Module):
         det = lambda p: p.detach()
         m, _ = ops.row_stats(x, want_std=False)
         z1 = ops.linear_fwd(m, det(se[1].weight).view(se[1].out_channels, -1), det(se[1].bias), relu=True)
-        st = _bn(z1.view(B, -1, 1), se[3], self.training)
+        st = ops.bn_coeffs(z1.view(B, -1, 1), se[3], self.training)
         z1n = ops.bn_apply(z1.view(B, -1, 1), st[2], st[3]).view(B, -1)
         z2 = ops.linear_fwd(z1n, det(se[4].weight).view(se[4].out_channels, -1), det(se[4].bias))
         out = torch.empty_like(x)
@@ -103,13 +103,13 @@ class Bottle2neck(nn.Module):
         det = lambda p: p.detach()
         training = self.training
         r1 = ops.conv1d_fwd(x, det(self.conv1.weight), det(self.conv1.bias), relu=True)
-        st1 = _bn(r1, self.bn1, training)
+        st1 = ops.bn_coeffs(r1, self.bn1, training)
         o1 = ops.bn_apply(r1, st1[2], st1[3])
         cat = torch.empty_like(o1)
         t_i = o1[:, :w]
         for i in range(nums):
             r_i = ops.conv1d_fwd(t_i, det(self.convs[i].weight), det(self.convs[i].bias), relu=True, dil=d, pad=d)
-            st_i = _bn(r_i, self.bns[i], training)
+            st_i = ops.bn_coeffs(r_i, self.bns[i], training)
             if i + 1 < nums:
                 t_next = torch.empty((B, w, T), device=x.device, dtype=torch.float32)
                 ops.res2_bn_apply(r_i, st_i[2], st_i[3], cat[:, i * w:(i + 1) * w], o1[:, (i + 1) * w:(i + 2) * w], t_next)
@@ -119,12 +119,12 @@ class Bottle2neck(nn.Module):
             t_i = t_next
         ops.add_strided(cat[:, nums * w:], o1[:, nums * w:])
         r3 = ops.conv1d_fwd(cat, det(self.conv3.weight), det(self.conv3.bias), relu=True)
-        st3 = _bn(r3, self.bn3, training)
+        st3 = ops.bn_coeffs(r3, self.bn3, training)
         o3 = ops.bn_apply(r3, st3[2], st3[3])
         se = self.se.se
         m, _ = ops.row_stats(o3, want_std=False)
         z1 = ops.linear_fwd(m, det(se[1].weight).view(se[1].out_channels, -1), det(se[1].bias), relu=True)
-        stS = _bn(z1.view(B, -1, 1), se[3], training)
+        stS = ops.bn_coeffs(z1.view(B, -1, 1), se[3], training)
         z1n = ops.bn_apply(z1.view(B, -1, 1), stS[2], stS[3]).view(B, -1)
         z2 = ops.linear_fwd(z1n, det(se[4].weight).view(se[4].out_channels, -1), det(se[4].bias))
         out = torch.empty_like(x)
@@ -141,35 +141,11 @@ def _forward_only(mod, x, name):
                                   "Res2Net2.forward" % name)
 
 
-def _bn(x3, bn, training):
-    """BatchNorm1d on a (B, C, S) tensor: returns (mean, invstd, scale, shift)."""
-    if training:
-        st = ops.bn_stats(x3, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                          bn.eps, bn.momentum)
-        ops.bn_tick(bn.num_batches_tracked)
-        return st
-    scale, shift = ops.bn_eval_coeffs(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                      bn.running_var, bn.eps)
-    return None, None, scale, shift
-
-
-class _EcapaFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        ctx.set_materialize_grads(False)
-        feat, out, saved = model._forward_impl(x, save=True)
-        ctx.model, ctx.saved = model, saved
-        return feat, out
-
-    @staticmethod
-    def backward(ctx, dfeat, dout):
-        model, saved = ctx.model, ctx.saved
-        ctx.saved = None
-        return (None, None) + tuple(model._backward_impl(saved, dfeat, dout))
-
-
-class Res2Net2(nn.Module):
+class Res2Net2(HipModel):
     TAIL = ("fc7.weight", "fc7.bias", "bn7.weight", "bn7.bias")  # no gradient under ang_iso: last in the arena
+    # layer4 + attention + bn5 + fc6 (15.7 of the 25 MB) leave as soon as layer4's weight gradient is enqueued,
+    # underneath the three Bottle2neck blocks' backward
+    BUCKET_BYTES = 8 << 20
 
     def __init__(self, block, C, model_scale, nOut, n_mels, encoder_type="ECA", context=True,
                  summed=False, out_bn=True, **kwargs):
@@ -210,14 +186,11 @@ class Res2Net2(nn.Module):
         self.fc7 = nn.Linear(256, nOut)
         self.bn7 = nn.BatchNorm1d(nOut)
         self.C = C
-        self._arena = None
         self.compute_dtype = "fp32"
-        self._bucketer = None  # dist.GradBucketer when the all-reduce is overlapped with backward
         # weight gradients on a side HIP stream (they feed nothing until the optimiser): the MFMA-bound GEMMs and the
         # small K = 3 kernels overlap the HBM-bound BatchNorm / pooling backward passes of the main stream.  A captured
         # hipGraph keeps them on the main stream: its fork / join pairs replay slower (profiles/README.md).
         self.overlap_wgrad = os.environ.get("AIR_OVERLAP_WGRAD", "1") == "1"
-        self._side_stream = None
         self.fuse_tap_stats = os.environ.get("AIR_TAP_STATS", "1") == "1"  # Res2 branch statistics from the conv epilogue
         self.fuse_pw_stats = os.environ.get("AIR_PW_STATS", "1") == "1"    # K = 1 convs: statistics from the GEMM epilogue
         # (round 6) Res2 chain: the elementwise pass in front of a branch conv is that conv's prologue (bf16-resident path)
@@ -227,61 +200,15 @@ class Res2Net2(nn.Module):
         # fused launch is 29.9 us where conv 14.8 + apply 9.4 were 24.2) - so forward on, backward off
         self.fuse_tap_prologue = int(os.environ.get("AIR_TAP_PROLOGUE", "1"))
 
-    def enable_ddp_overlap(self, bucket_bytes=8 << 20):
-        """Launch the gradient all-reduce from inside backward (one process per GPU, world size > 1):
-        layer4 + attention + bn5 + fc6 (15.7 of the 25 MB) leave as soon as layer4's weight gradient is
-        enqueued, underneath the three Bottle2neck blocks' backward."""
-        from .dist import GradBucketer
-        self._bucketer = GradBucketer(bucket_bytes)
-        return self
-
-    def __getstate__(self):
-        """Whole-module pickles (main_train.py:675-704): the flat arenas are rebuilt on first use."""
-        st = dict(self.__dict__)
-        st["_arena"] = None
-        st["_bucketer"] = None
-        st["_segment_cut"] = None
-        st["_side_stream"] = None
-        return st
-
     def set_compute_dtype(self, dtype):
         if dtype not in ("fp32", "bf16", "bf16c"):
             raise ValueError("compute_dtype must be 'fp32', 'bf16' or 'bf16c', got %r" % (dtype,))
         self.compute_dtype = dtype
         return self
 
-    def forward_saved(self, x):
-        """The train-mode forward WITHOUT autograd: (feat, saved) - see ResNet.forward_saved."""
-        x = x.float().contiguous()
-        self.arena()
-        feat, out, saved = self._forward_impl(x, save=True)
-        saved["logits"] = out  # the CE head's input (train.Trainer, add_loss=None)
-        return feat, saved
-
-    def backward_saved(self, saved, dfeat, dout=None):
-        """dout: the gradient of saved["logits"] (the CE head through fc7 / bn7), or None."""
-        return self._backward_impl(saved, dfeat, dout)
-
-    # ------------------------------------------------------------------ plumbing
-    def arena(self):
-        dev = self.conv1.weight.device
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()), tail_names=self.TAIL)
-        if not self._arena.bound() or self._arena.device != dev:
-            self._arena.bind(dev)
-        return self._arena
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _hip.AirError("Res2Net2 HIP path needs a GPU tensor; there is no CPU fallback")
+    def check_input(self, x):
         if x.dim() != 3 or x.shape[1] != self.n_mfcc:
             raise ValueError("Res2Net2 expects (B, %d, T), got %s" % (self.n_mfcc, tuple(x.shape)))
-        x = x.float().contiguous()
-        arena = self.arena()
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p, _, _ in arena.entries):
-            return _EcapaFn.apply(self, x, *[p for _, p, _, _ in arena.entries])
-        feat, out, _ = self._forward_impl(x, save=False)
-        return feat, out
 
     # ------------------------------------------------------------------ forward
     def _block_fwd(self, blk, inp, out, training, save, out_bf=None):
@@ -291,7 +218,7 @@ class Res2Net2(nn.Module):
         det = lambda p: p.detach()
         bf = getattr(self, "_bf16c_now", self.compute_dtype == "bf16c")
         r1 = ops.conv1d_fwd(inp, det(blk.conv1.weight), det(blk.conv1.bias), relu=True, bf16=bf)
-        st1 = _bn(r1, blk.bn1, training)
+        st1 = ops.bn_coeffs(r1, blk.bn1, training)
         o1 = ops.bn_apply(r1, st1[2], st1[3])
         cat = torch.empty_like(o1)
         # bf16 training: the concat's bf16 copy (conv3's weight-gradient operand) is written by the passes that fill it
@@ -304,7 +231,7 @@ class Res2Net2(nn.Module):
         for i in range(nums):
             r_i = ops.conv1d_fwd(t_i, det(blk.convs[i].weight), det(blk.convs[i].bias), relu=True,
                                  dil=d, pad=d, bf16=bf, w_packed=wp[i] if wp is not None else None)
-            st_i = _bn(r_i, blk.bns[i], training)
+            st_i = ops.bn_coeffs(r_i, blk.bns[i], training)
             # BN-apply, store into the concat slice and form the next branch's input in one pass
             if i + 1 < nums:
                 t_next = torch.empty((B, w, T), device=inp.device, dtype=torch.float32)
@@ -319,7 +246,7 @@ class Res2Net2(nn.Module):
             t_i = t_next
         ops.add_strided(cat[:, nums * w:], o1[:, nums * w:], out_bf=cb(nums * w, C))
         r3 = ops.conv1d_fwd(cat, det(blk.conv3.weight), det(blk.conv3.bias), relu=True, bf16=bf)
-        st3 = _bn(r3, blk.bn3, training)
+        st3 = ops.bn_coeffs(r3, blk.bn3, training)
         se = blk.se.se
         if 32 <= T <= 1024:  # the SE squeeze (mean over time) comes out of the pass that writes o3
             m = torch.empty((B, C), device=inp.device, dtype=torch.float32)
@@ -328,7 +255,7 @@ class Res2Net2(nn.Module):
             o3 = ops.bn_apply(r3, st3[2], st3[3])
             m, _ = ops.row_stats(o3, want_std=False)
         z1 = ops.linear_fwd(m, det(se[1].weight).view(se[1].out_channels, -1), det(se[1].bias), relu=True)
-        stS = _bn(z1.view(B, -1, 1), se[3], training)
+        stS = ops.bn_coeffs(z1.view(B, -1, 1), se[3], training)
         z1n = ops.bn_apply(z1.view(B, -1, 1), stS[2], stS[3]).view(B, -1)
         z2 = ops.linear_fwd(z1n, det(se[4].weight).view(se[4].out_channels, -1), det(se[4].bias))
         ops.se_scale_fwd(o3, z2, inp, out, out_bf=out_bf)
@@ -362,7 +289,7 @@ class Res2Net2(nn.Module):
         B, _, T = x.shape
         C = self.C
         r0 = ops.conv1d_fwd(x, det(self.conv1.weight), det(self.conv1.bias), relu=True, pad=2)  # :159-160
-        st0 = _bn(r0, self.bn1, training)
+        st0 = ops.bn_coeffs(r0, self.bn1, training)
         # bf16 training: the first block's input and attention's hidden tensor leave their BatchNorm with a bf16 copy
         # (X operands of the conv1 / attention.3 weight gradients)
         h_bf = ops.bf16_rows(None, B, C, T, x.device) if (bf and save) else None
@@ -408,7 +335,7 @@ class Res2Net2(nn.Module):
             ctx, w_c, ctxb = None, None, None
             w_x = det(a0.weight)
         a1 = ops.conv1d_fwd(x4, w_x, det(a0.bias), bias_bc=ctxb, relu=True, bf16=bf)  # attention.0 + ReLU
-        stA = _bn(a1, self.attention[2], training)
+        stA = ops.bn_coeffs(a1, self.attention[2], training)
         a1n_bf = ops.bf16_rows(None, B, a1.shape[1], T, x.device) if (bf and save) else None
         a1n = ops.bn_apply(a1, stA[2], stA[3], y_bf=a1n_bf)
         w3, b3 = det(a3.weight), det(a3.bias)
@@ -417,14 +344,14 @@ class Res2Net2(nn.Module):
             b3 = b3.expand(x4.shape[1]).contiguous()
         wts = ops.conv1d_fwd(a1n, w3, b3, bf16=bf)  # logits -> softmax weights below
         pooled = ops.asp_fwd(x4, wts)  # :184-187 (mu | sg)
-        st5 = _bn(pooled.view(B, -1, 1), self.bn5, training)
+        st5 = ops.bn_coeffs(pooled.view(B, -1, 1), self.bn5, training)
         p5 = ops.bn_apply(pooled.view(B, -1, 1), st5[2], st5[3]).view(B, -1)
         feat = ops.linear_fwd(p5, det(self.fc6.weight), det(self.fc6.bias))  # :191
         o7 = ops.linear_fwd(feat, det(self.fc7.weight), det(self.fc7.bias))  # :193
         st7 = None
         out = o7
         if self.out_bn:
-            st7 = _bn(o7.view(B, -1, 1), self.bn7, training)
+            st7 = ops.bn_coeffs(o7.view(B, -1, 1), self.bn7, training)
             out = ops.bn_apply(o7.view(B, -1, 1), st7[2], st7[3]).view(B, -1)
         S = None
         if save:
@@ -510,7 +437,7 @@ class Res2Net2(nn.Module):
         arena = self.arena()
         # weight gradients on the side stream (schedule.py; see __init__), each bf16 operand copy they read in its own
         # buffer; an accumulating pass runs as one chain
-        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=False)
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, self._bucketer, side_when_accumulating=False)
         G, on_side = sch.G, sch.on_side
         det = lambda p: p.detach()
         bf = S.get("bf16c", self.compute_dtype == "bf16c")
@@ -727,7 +654,7 @@ class Res2Net2(nn.Module):
         o3 = oh.bn_apply(r3, T, st3[2], st3[3], rowmean=m)  # + the SE squeeze of the stored tensor
         se = blk.se.se
         z1 = ops.linear_fwd(m, det(se[1].weight).view(se[1].out_channels, -1), det(se[1].bias), relu=True)
-        stS = _bn(z1.view(B, -1, 1), se[3], training)
+        stS = ops.bn_coeffs(z1.view(B, -1, 1), se[3], training)
         z1n = ops.bn_apply(z1.view(B, -1, 1), stS[2], stS[3]).view(B, -1)
         z2 = ops.linear_fwd(z1n, det(se[4].weight).view(se[4].out_channels, -1), det(se[4].bias))
         oh.se_scale_fwd(o3, z2, inp, T, out)
@@ -775,14 +702,14 @@ class Res2Net2(nn.Module):
         a1n = oh.bn_apply(a1, T, stA[2], stA[3])
         wts = oh.conv_pointwise(a1n, det(a3.weight), T, bias=det(a3.bias))  # logits -> softmax weights below
         pooled = oh.asp_fwd(x4, wts, T)  # :184-187 (mu | sg)
-        st5 = _bn(pooled.view(B, -1, 1), self.bn5, training)
+        st5 = ops.bn_coeffs(pooled.view(B, -1, 1), self.bn5, training)
         p5 = ops.bn_apply(pooled.view(B, -1, 1), st5[2], st5[3]).view(B, -1)
         feat = ops.linear_fwd(p5, det(self.fc6.weight), det(self.fc6.bias))  # :191
         o7 = ops.linear_fwd(feat, det(self.fc7.weight), det(self.fc7.bias))  # :193
         st7 = None
         out = o7
         if self.out_bn:
-            st7 = _bn(o7.view(B, -1, 1), self.bn7, training)
+            st7 = ops.bn_coeffs(o7.view(B, -1, 1), self.bn7, training)
             out = ops.bn_apply(o7.view(B, -1, 1), st7[2], st7[3]).view(B, -1)
         S = None
         if save:
@@ -872,7 +799,7 @@ class Res2Net2(nn.Module):
 
     def _backward_h(self, S, dfeat, dout):
         arena = self.arena()
-        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=False)
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, self._bucketer, side_when_accumulating=False)
         G, on_side = sch.G, sch.on_side
         det = lambda p: p.detach()
         B, _, T = S["x"].shape

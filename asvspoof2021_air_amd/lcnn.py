@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip, ops
-from .arena import ParamArena
+from .hip_model import HipModel
 from .schedule import BackwardSchedule
 
 # (name, Cin, Cout, kernel, padding, max-pool, BatchNorm) of conv2 .. conv9 (model.py:531-563)
@@ -63,24 +63,15 @@ class MaxFeatureMap2D(nn.Module):
         return y.view((shp[0], shp[1] // 2) + tuple(shp[2:]))
 
 
-class _LCNNFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        ctx.set_materialize_grads(False)
-        feat, out, saved = model._forward_impl(x, save=True)
-        ctx.model = model
-        ctx.saved = saved
-        return feat, out
+class LCNN(HipModel):
+    TAIL = ("fc_mu.weight", "fc_mu.bias")
+    # 3.5 MB of gradients (2.8 MB of them out.1): 256 KB buckets send out.1 + out.3, conv9 .. conv6 and conv5 .. conv3
+    # from inside backward; the default 16 MB bucket would leave the whole exchange behind it
+    BUCKET_BYTES = 256 << 10
+    # the offset of the mask's Philox stream as a device-side counter (HipModel.device_counter)
+    _mask_ctr = None
+    _mask_ctrs = None
 
-    @staticmethod
-    def backward(ctx, dfeat, dout):
-        model, saved = ctx.model, ctx.saved
-        ctx.saved = None
-        grads = model._backward_impl(saved, dfeat, dout)
-        return (None, None) + tuple(grads)
-
-
-class LCNN(nn.Module):
     def __init__(self, num_nodes, enc_dim, nclasses=2):
         super().__init__()
         self.num_nodes = num_nodes
@@ -107,54 +98,20 @@ class LCNN(nn.Module):
         self._mask_tensor = None
         self._mask_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self._mask_offset = 0
-        self._mask_ctr = None
-        self._mask_ctrs = None
-        self._arena = None
         self._unit = {}   # device -> (ones, zeros) of 64: the affine=False BatchNorms' scale and shift
         self._wpad = {}   # layer name -> weight zero-padded to a multiple of 64 rows (conv3, conv4)
-        # weight gradients on a side HIP stream (schedule.py); train.Trainer turns it off for its hipGraph capture
-        self.overlap_wgrad = True
-        self._side_stream = None
-        self._bucketer = None     # dist.GradBucketer when the all-reduce is overlapped with backward
-        self._segment_cut = None  # train.Trainer's capture-segment hook (schedule.BackwardSchedule)
-
-    def enable_ddp_overlap(self, bucket_bytes=256 << 10):
-        """Launch the gradient all-reduce from inside backward (one process per GPU, world size > 1).  The LCNN has
-        3.5 MB of gradients (2.8 MB of them out.1): 256 KB buckets send out.1 + out.3, conv9 .. conv6 and conv5 ..
-        conv3 from inside backward; the default 16 MB bucket would leave the whole exchange behind it."""
-        from .dist import GradBucketer
-        self._bucketer = GradBucketer(bucket_bytes)
-        return self
 
     def __getstate__(self):
-        """Whole-module pickles (main_train.py:675-704 -> generate_score.py:46-48): arenas, streams, padded weights
-        and an installed mask are runtime state, rebuilt on first use; the device-side mask counter travels as its
-        value."""
-        st = dict(self.__dict__)
-        st["_arena"] = None
-        st["_side_stream"] = None
-        st["_bucketer"] = None
-        st["_segment_cut"] = None
+        """Also runtime state: the unit coefficients, the padded weights and an installed mask."""
+        st = super().__getstate__()
         st["_unit"], st["_wpad"] = {}, {}
         st["_mask_tensor"] = None
-        if st.get("_mask_ctr") is not None:
-            st["_mask_offset"] = int(st["_mask_ctr"].item())
-        st["_mask_ctr"] = None
-        st["_mask_ctrs"] = None
+        self.fold_counter(st, "_mask")
         if st.get("noise_mode") == "tensor":
             st["noise_mode"] = "device"
         return st
 
     # ------------------------------------------------------------------ plumbing
-    def arena(self):
-        """Flat parameter/gradient arenas (built lazily, rebuilt after .to(device)); fc_mu is the tail."""
-        dev = self.fc_mu.weight.device
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()), tail_names=("fc_mu.weight", "fc_mu.bias"))
-        if not self._arena.bound() or self._arena.device != dev:
-            self._arena.bind(dev)
-        return self._arena
-
     def set_dropout_mask(self, mask):
         """Install the (B, 4416) scaled keep-mask nn.Dropout(0.7) would draw (values 0 and 1 / 0.3), or None to go
         back to the device draw."""
@@ -167,19 +124,7 @@ class LCNN(nn.Module):
             if tuple(m.shape) != (B, N):
                 raise _hip.AirError("dropout mask must be (B, %d), got %s" % (N, tuple(m.shape)))
             return m.to(device=device, dtype=torch.float32).contiguous()
-        # ONE counter per device, never replaced once made: a captured hipGraph holds its address (see
-        # resnet.ResNet._draw_noise); moving devices carries the live count over
-        ctrs = self._mask_ctrs
-        if ctrs is None:
-            ctrs = self._mask_ctrs = {}
-        ctr = ctrs.get(device)
-        if ctr is None:
-            if self._mask_ctr is not None:
-                self._mask_offset = int(self._mask_ctr.item())
-            ctr = ctrs[device] = torch.tensor([self._mask_offset], dtype=torch.int64, device=device)
-        elif self._mask_ctr is not None and self._mask_ctr is not ctr:
-            ctr.copy_(self._mask_ctr)
-        self._mask_ctr = ctr
+        ctr = self.device_counter("_mask", device)
         return ops.dropout_mask_ctr((B, N), DROPOUT_P, self._mask_seed, ctr, device)
 
     def _units(self, device):
@@ -212,33 +157,6 @@ class LCNN(nn.Module):
                              "needs T // 16 = %d and F // 16 = %d (model.py:601)" % (
                                  H, W, H // 16, W // 16, got, want, 750 // 16, self.num_nodes // 16))
 
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _hip.AirError("LCNN HIP path needs a GPU tensor; there is no CPU fallback")
-        self.check_input(x)
-        x = x.float().contiguous()  # main_train.py:338 hands over a transposed view
-        arena = self.arena()
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p, _, _ in arena.entries):
-            params = [p for _, p, _, _ in arena.entries]
-            return _LCNNFn.apply(self, x, *params)
-        feat, out, _ = self._forward_impl(x, save=False)
-        return feat, out
-
-    def forward_saved(self, x):
-        """The train-mode forward WITHOUT autograd: (feat, saved); with ``backward_saved`` what _LCNNFn does, from one
-        Python thread (train.Trainer's capture)."""
-        self.check_input(x)
-        x = x.float().contiguous()
-        self.arena()
-        feat, out, saved = self._forward_impl(x, save=True)
-        saved["logits"] = out  # the CE head's input (train.Trainer, add_loss=None)
-        return feat, saved
-
-    def backward_saved(self, saved, dfeat, dout=None):
-        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order.
-        dout: the gradient of saved["logits"] (the CE head), or None."""
-        return self._backward_impl(saved, dfeat, dout)
-
     # ------------------------------------------------------------------ forward
     def _forward_impl(self, x, save):
         training = self.training
@@ -254,20 +172,11 @@ class LCNN(nn.Module):
             w = self._weight(name)
             pre = ops.conv2d_fwd(cur, w, 1, pad)
             m, route = ops.mfm_pool_fwd(pre, C=cout, bias=seq[0].bias.detach(), pool=pool)
-            st = None
+            st, a = None, m
             if bn:
-                bnm = seq[-1]
                 C = cout // 2
-                if training:
-                    mean, invstd, scale, shift = ops.bn_stats(m, ones[:C], zeros[:C], bnm.running_mean, bnm.running_var,
-                                                              bnm.eps, bnm.momentum)
-                    ops.bn_tick(bnm.num_batches_tracked)
-                    st = (mean, invstd)
-                else:
-                    scale, shift = ops.bn_eval_coeffs(ones[:C], zeros[:C], bnm.running_mean, bnm.running_var, bnm.eps)
-                a = ops.bn_apply(m, scale, shift)
-            else:
-                a = m
+                st = ops.bn_coeffs(m, seq[-1], training, affine=(ones[:C], zeros[:C]))
+                a = ops.bn_apply(m, st[2], st[3])
             if save:
                 S["layers"].append((name, cur, w, pre.shape, pool, route, m, st))
             cur = a
@@ -295,13 +204,7 @@ class LCNN(nn.Module):
     def _backward_impl(self, S, dfeat, dout):
         arena = self.arena()
         sch = BackwardSchedule(self, arena, self.overlap_wgrad, self._bucketer, side_when_accumulating=True)
-        G = sch.G
-        have = set()
-
-        def gv(name):
-            have.add(name)
-            return G[name]
-
+        gv = sch.grad
         dev = S["x"].device
         ones, zeros = self._units(dev)
         if dout is not None:  # CE / base-loss branch (main_train.py:355); dead under ang_iso
@@ -345,4 +248,4 @@ class LCNN(nn.Module):
         x, r1 = S["x"], S["r1"]
         gw1, gb1 = gv("conv1.0.weight"), gv("conv1.0.bias")
         sch.on_side(lambda: ops.lcnn_conv1_wgrad(x, da, r1, gw1, gb1), x, da, r1)
-        return sch.finish(have.__contains__, "fc_mu.weight" in have)
+        return sch.finish()

@@ -298,6 +298,20 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=1e-5):
     return coef[0], coef[1]
 
 
+def bn_coeffs(x, bn, training, stats_in=None, affine=None):
+    """(mean, invstd, scale, shift) of the BatchNorm module ``bn`` over x.  Training: batch statistics, the running
+    statistics updated and num_batches_tracked queued for bn_flush().  Otherwise (None, None, scale, shift) from the
+    running statistics.  stats_in: see bn_stats.  affine: the (gamma, beta) of a layer that has none of its own
+    (BatchNorm2d(affine=False): unit scale, zero shift)."""
+    gamma, beta = affine if affine is not None else (bn.weight.detach(), bn.bias.detach())
+    if training:
+        st = bn_stats(x, gamma, beta, bn.running_mean, bn.running_var, bn.eps, bn.momentum, stats_in=stats_in)
+        bn_tick(bn.num_batches_tracked)
+        return st
+    scale, shift = bn_eval_coeffs(gamma, beta, bn.running_mean, bn.running_var, bn.eps)
+    return None, None, scale, shift
+
+
 def bn_apply(x, scale, shift, relu=False, out=None, rowmean=None, y_bf=None):
     """y = x * scale[c] + shift[c] (+ ReLU); rowmean (B, C), 32 <= S <= 1024: also the mean over s of every
     output plane (the SE squeeze taken on the way out)."""

@@ -22,8 +22,8 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _hip, ops
-from .arena import ParamArena
+from . import ops
+from .hip_model import HipModel
 from .schedule import BackwardSchedule
 
 
@@ -87,24 +87,10 @@ def _v3(t):
     return t.view(B, C, H * W)
 
 
-class _Res2NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        ctx.set_materialize_grads(False)
-        feat, out, saved = model._forward_impl(x, save=True)
-        ctx.model = model
-        ctx.saved = saved
-        return feat, out
+class Res2Net(HipModel):
+    TAIL = ("cls_layer.weight", "cls_layer.bias")
+    BUCKET_BYTES = 256 << 10  # buckets go out as the blocks of layer4 .. layer1 finish their weight gradients
 
-    @staticmethod
-    def backward(ctx, dfeat, dout):
-        model, saved = ctx.model, ctx.saved
-        ctx.saved = None
-        grads = model._backward_impl(saved, dfeat, dout)
-        return (None, None) + tuple(grads)
-
-
-class Res2Net(nn.Module):
     def __init__(self, block, layers, baseWidth=26, scale=4, m=0.35, num_classes=1000, loss='softmax', **kwargs):
         self.inplanes = 16
         super().__init__()
@@ -133,12 +119,6 @@ class Res2Net(nn.Module):
             elif isinstance(mod, nn.BatchNorm2d):
                 nn.init.constant_(mod.weight, 1)
                 nn.init.constant_(mod.bias, 0)
-        self._arena = None
-        # weight gradients on a side HIP stream (schedule.py); train.Trainer turns it off for its hipGraph capture
-        self.overlap_wgrad = True
-        self._side_stream = None
-        self._bucketer = None     # dist.GradBucketer when the all-reduce is overlapped with backward
-        self._segment_cut = None  # train.Trainer's capture-segment hook (schedule.BackwardSchedule)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None
@@ -154,23 +134,6 @@ class Res2Net(nn.Module):
         for _ in range(1, blocks):
             layers.append(block(self.inplanes, planes, baseWidth=self.baseWidth, scale=self.scale))
         return nn.Sequential(*layers)
-
-    def enable_ddp_overlap(self, bucket_bytes=256 << 10):
-        """Launch the gradient all-reduce from inside backward (one process per GPU, world size > 1): 256 KB buckets
-        go out as the blocks of layer4 .. layer1 finish their weight gradients."""
-        from .dist import GradBucketer
-        self._bucketer = GradBucketer(bucket_bytes)
-        return self
-
-    def __getstate__(self):
-        """Whole-module pickles (main_train.py:675-704 -> generate_score.py:46-48): arenas and streams are runtime
-        state, rebuilt on first use."""
-        st = dict(self.__dict__)
-        st["_arena"] = None
-        st["_side_stream"] = None
-        st["_bucketer"] = None
-        st["_segment_cut"] = None
-        return st
 
     # ------------------------------------------------------------------ plumbing
     def blocks(self):
@@ -201,66 +164,16 @@ class Res2Net(nn.Module):
                 if k not in (1, 2):
                     raise NotImplementedError("Res2Net HIP path: downsample pool of kernel %s" % (k,))
 
-    def arena(self):
-        """Flat parameter/gradient arenas (built lazily, rebuilt after .to(device)); cls_layer is the tail."""
-        dev = self.cls_layer.weight.device
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()),
-                                     tail_names=("cls_layer.weight", "cls_layer.bias"))
-        if not self._arena.bound() or self._arena.device != dev:
-            self._arena.bind(dev)
-        return self._arena
-
     def check_input(self, x):
         if x.dim() != 4 or x.shape[1] != 1:
             raise ValueError("Res2Net expects (B, 1, F, T), got %s" % (tuple(x.shape),))
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _hip.AirError("Res2Net HIP path needs a GPU tensor; there is no CPU fallback")
-        self.check_input(x)
         self.check_supported()
-        x = x.float().contiguous()  # main_train.py:338 hands over a transposed view
-        arena = self.arena()
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p, _, _ in arena.entries):
-            params = [p for _, p, _, _ in arena.entries]
-            return _Res2NetFn.apply(self, x, *params)
-        feat, out, _ = self._forward_impl(x, save=False)
-        return feat, out
 
     def extract(self, x):
         """model.py:355-374: the pooled 256-dim embedding."""
         return self.forward(x)[0]
 
-    def forward_saved(self, x):
-        """The train-mode forward WITHOUT autograd: (feat, saved); with ``backward_saved`` what _Res2NetFn does, from
-        one Python thread (train.Trainer's capture)."""
-        self.check_input(x)
-        self.check_supported()
-        x = x.float().contiguous()
-        self.arena()
-        feat, out, saved = self._forward_impl(x, save=True)
-        saved["logits"] = out  # the CE head's input (train.Trainer, add_loss=None): the log-probabilities
-        return feat, saved
-
-    def backward_saved(self, saved, dfeat, dout=None):
-        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order.
-        dout: the gradient of saved["logits"] (the CE head), or None."""
-        return self._backward_impl(saved, dfeat, dout)
-
     # ------------------------------------------------------------------ layers
-    def _bn(self, bnm, x):
-        """(scale, shift, (mean, invstd) or None) of a BatchNorm2d over x: batch statistics (running statistics
-        updated) in training mode, running statistics in eval mode."""
-        if self.training:
-            mean, invstd, scale, shift = ops.bn_stats(x, bnm.weight.detach(), bnm.bias.detach(), bnm.running_mean,
-                                                      bnm.running_var, bnm.eps, bnm.momentum)
-            ops.bn_tick(bnm.num_batches_tracked)
-            return scale, shift, (mean, invstd)
-        scale, shift = ops.bn_eval_coeffs(bnm.weight.detach(), bnm.bias.detach(), bnm.running_mean, bnm.running_var,
-                                          bnm.eps)
-        return scale, shift, None
-
     @staticmethod
     def _c1_fwd(x, w):
         cout, cin = w.shape[:2]
@@ -290,8 +203,8 @@ class Res2Net(nn.Module):
         w, nums, stage = blk.width, blk.nums, blk.stype == 'stage'
         s = blk.convs[0].stride[0]
         c1 = self._c1_fwd(x, blk.conv1.weight.detach())  # model.py:452-455
-        sc1, sh1, st1 = self._bn(blk.bn1, c1)
-        out1 = ops.bn_apply(c1, sc1, sh1, relu=True)
+        st1 = ops.bn_coeffs(c1, blk.bn1, self.training)
+        out1 = ops.bn_apply(c1, st1[2], st1[3], relu=True)
         H, W = out1.shape[2], out1.shape[3]
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
         cat = torch.empty((B, w * blk.scale, Ho, Wo), device=x.device, dtype=torch.float32)
@@ -299,7 +212,8 @@ class Res2Net(nn.Module):
         sp = out1[:, 0:w]
         for i in range(nums):  # model.py:458-470
             ci = ops.conv_narrow_fwd(sp, blk.convs[i].weight.detach(), s)
-            sci, shi, sti = self._bn(blk.bns[i], ci)
+            sti = ops.bn_coeffs(ci, blk.bns[i], self.training)
+            sci, shi = sti[2], sti[3]
             nxt = None
             if not stage and i + 1 < nums:
                 nxt = torch.empty((B, w, Ho, Wo), device=x.device, dtype=torch.float32)
@@ -315,8 +229,8 @@ class Res2Net(nn.Module):
         else:
             ops.add_strided(_v3(cat_last), _v3(last))
         c3 = self._c1_fwd(cat, blk.conv3.weight.detach())
-        sc3, sh3, st3 = self._bn(blk.bn3, c3)
-        u = ops.bn_apply(c3, sc3, sh3)
+        st3 = ops.bn_coeffs(c3, blk.bn3, self.training)
+        u = ops.bn_apply(c3, st3[2], st3[3])
         m, _ = ops.row_stats(_v3(u), want_std=False)  # SELayer (model.py:499-505)
         fc1, fc2 = blk.se.fc[0], blk.se.fc[2]
         h = ops.linear_fwd(m, fc1.weight.detach(), None, relu=True)
@@ -326,8 +240,8 @@ class Res2Net(nn.Module):
             k = blk.downsample[0].kernel_size
             xp = x if k == 1 else ops.avgpool2d_fwd(x, k, k, 0, True, False)
             cd = self._c1_fwd(xp, blk.downsample[1].weight.detach())
-            scd, shd, std_ = self._bn(blk.downsample[2], cd)
-            r = ops.bn_apply(cd, scd, shd)
+            std_ = ops.bn_coeffs(cd, blk.downsample[2], self.training)
+            r = ops.bn_apply(cd, std_[2], std_[3])
             ds = (k, xp, cd, std_)
         else:
             r = x
@@ -345,14 +259,14 @@ class Res2Net(nn.Module):
         c = self.conv1
         # stem (model.py:261-266, :326-329): each BatchNorm + ReLU is the next convolution's prologue
         a0 = ops.conv_narrow_fwd(x, c[0].weight.detach(), 1)
-        s0, h0, st0 = self._bn(c[1], a0)
-        a1 = ops.conv_narrow_fwd(a0, c[3].weight.detach(), 1, in_scale=s0, in_shift=h0, relu=True)
-        s1, h1, st1 = self._bn(c[4], a1)
-        a2 = ops.conv_narrow_fwd(a1, c[6].weight.detach(), 1, in_scale=s1, in_shift=h1, relu=True)
-        s2, h2, st2 = self._bn(self.bn1, a2)
-        cur = ops.bn_apply(a2, s2, h2, relu=True)
+        st0 = ops.bn_coeffs(a0, c[1], self.training)
+        a1 = ops.conv_narrow_fwd(a0, c[3].weight.detach(), 1, in_scale=st0[2], in_shift=st0[3], relu=True)
+        st1 = ops.bn_coeffs(a1, c[4], self.training)
+        a2 = ops.conv_narrow_fwd(a1, c[6].weight.detach(), 1, in_scale=st1[2], in_shift=st1[3], relu=True)
+        st2 = ops.bn_coeffs(a2, self.bn1, self.training)
+        cur = ops.bn_apply(a2, st2[2], st2[3], relu=True)
         if save:
-            S.update(a0=a0, a1=a1, a2=a2, stem=((s0, h0, st0), (s1, h1, st1), st2))
+            S.update(a0=a0, a1=a1, a2=a2, stem=(st0, st1, st2))
         for name, blk in self.blocks():
             cur, bs = self._block_fwd(blk, cur, save)
             if save:
@@ -366,7 +280,8 @@ class Res2Net(nn.Module):
         return feat, out, S
 
     # ----------------------------------------------------------------- backward
-    def _block_bwd(self, blk, name, S, do, sch, gv):
+    def _block_bwd(self, blk, name, S, do, sch):
+        gv = sch.grad
         w, nums, stage = blk.width, blk.nums, blk.stype == 'stage'
         s = blk.convs[0].stride[0]
         x, u, z, o = S["x"], S["u"], S["z"], S["o"]
@@ -432,13 +347,7 @@ class Res2Net(nn.Module):
     def _backward_impl(self, S, dfeat, dout):
         arena = self.arena()
         sch = BackwardSchedule(self, arena, self.overlap_wgrad, self._bucketer, side_when_accumulating=True)
-        G = sch.G
-        have = set()
-
-        def gv(name):
-            have.add(name)
-            return G[name]
-
+        gv = sch.grad
         feat = S["feat"]
         if dout is not None:  # CE / base-loss branch (main_train.py:355): log_softmax, then cls_layer
             dlog = ops.log_softmax_bwd(S["out"], dout.contiguous())
@@ -453,11 +362,12 @@ class Res2Net(nn.Module):
         ops.row_stats_bwd(_v3(top), feat, None, dfeat, None, _v3(dtop), accumulate=False)
         d = dtop
         for name, blk, bs in reversed(S["blocks"]):
-            d = self._block_bwd(blk, name, bs, d, sch, gv)
+            d = self._block_bwd(blk, name, bs, d, sch)
             sch.grads_final_from(name + ".conv1.weight")
         # stem
         c = self.conv1
-        (s0, h0, st0), (s1, h1, st1), st2 = S["stem"]
+        st0, st1, st2 = S["stem"]  # (mean, invstd, scale, shift) each
+        (s0, h0), (s1, h1) = st0[2:], st1[2:]
         x, a0, a1, a2 = S["x"], S["a0"], S["a1"], S["a2"]
         da2, _, _ = ops.bn_bwd(a2, d, st2[0], st2[1], self.bn1.weight.detach(), self.bn1.bias.detach(), relu=True,
                                dgamma=gv("bn1.weight"), dbeta=gv("bn1.bias"))
@@ -475,4 +385,4 @@ class Res2Net(nn.Module):
                                dgamma=gv("conv1.1.weight"), dbeta=gv("conv1.1.bias"))
         w0, g0 = c[0].weight.detach(), gv("conv1.0.weight")
         sch.on_side(lambda: ops.conv_narrow_wgrad(x, da0, w0.shape, 1, out=g0), x, da0)
-        return sch.finish(have.__contains__, "cls_layer.weight" in have)
+        return sch.finish()

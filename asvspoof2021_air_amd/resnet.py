@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from . import _hip, ops
-from .arena import ParamArena
+from .hip_model import HipModel
 from .schedule import BackwardSchedule, side_stream
 
 
@@ -77,11 +77,11 @@ class PreActBlock(nn.Module):
                                       "through ResNet.forward")
         x = x.float().contiguous()
         w = lambda conv: conv.weight.detach()
-        st1 = _bn_train_coeffs(x, self.bn1, self.training)
+        st1 = ops.bn_coeffs(x, self.bn1, self.training)
         a1 = ops.bn_apply(x, st1[2], st1[3], relu=True)
         sc = ops.conv2d_fwd(a1, w(self.shortcut[0]), self.stride, 0) if hasattr(self, "shortcut") else x
         h = ops.conv2d_fwd(a1, w(self.conv1), self.stride, 1)
-        st2 = _bn_train_coeffs(h, self.bn2, self.training)
+        st2 = ops.bn_coeffs(h, self.bn2, self.training)
         out = ops.conv2d_fwd(ops.bn_apply(h, st2[2], st2[3], relu=True), w(self.conv2), 1, 1, residual=sc)
         ops.bn_flush()
         return out
@@ -92,42 +92,14 @@ RESNET_CONFIGS = {"18": [[2, 2, 2, 2], PreActBlock],
                   "34": [[3, 4, 6, 3], PreActBlock]}
 
 
-def _bn_train_coeffs(x, bn, training, stats_in=None):
-    """(mean, invstd, scale, shift) for BatchNorm ``bn`` on ``x``.  stats_in: statistics records of ``x`` from the
-    epilogue of the convolution that produced it (ops.conv2d_fwd(..., stats=True)), or None."""
-    if training:
-        mean, invstd, scale, shift = ops.bn_stats(x, bn.weight.detach(), bn.bias.detach(),
-                                                  bn.running_mean, bn.running_var, bn.eps,
-                                                  bn.momentum, stats_in=stats_in)
-        ops.bn_tick(bn.num_batches_tracked)
-        return mean, invstd, scale, shift
-    scale, shift = ops.bn_eval_coeffs(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                      bn.running_var, bn.eps)
-    return None, None, scale, shift
-
-
-class _ResNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x, noise, *params):
-        ctx.set_materialize_grads(False)
-        feat, mu, saved = model._forward_impl(x, noise, save=True)
-        ctx.model = model
-        ctx.saved = saved
-        if getattr(model, "keep_saved_for_test", False):  # parity tests read the ReLU decisions of the step
-            model._last_saved_for_test = saved
-        return feat, mu
-
-    @staticmethod
-    def backward(ctx, dfeat, dmu):
-        model, saved = ctx.model, ctx.saved
-        ctx.saved = None
-        grads = model._backward_impl(saved, dfeat, dmu)
-        return (None, None, None) + tuple(grads)
-
-
-class ResNet(nn.Module):
+class ResNet(HipModel):
     MAX_POOL_FRAMES = 148  # csrc/pool_head.hip: (256 (T' + 1) + 2 T') floats <= 150 KB of LDS: the LDS-resident kernel
     MAX_POOL_FRAMES_GLOBAL = 12000  # its in-place variant: (3 T' + 3 x 256) floats of per-frame vectors in LDS
+    TAIL = ("fc_mu.weight", "fc_mu.bias")
+    # the offset of the Philox stream as a device-side counter (HipModel.device_counter); class-level, so that a
+    # pickle from before the per-device counters loads
+    _noise_ctr = None
+    _noise_ctrs = None
 
     def __init__(self, num_nodes, enc_dim, resnet_type="18", nclasses=2):
         self.in_planes = 16
@@ -155,8 +127,6 @@ class ResNet(nn.Module):
         self._noise_tensor = None
         self._noise_seed = int(torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF
         self._noise_offset = 0
-        self._noise_ctr = None  # the offset of the Philox stream as a device-side counter (ops.randn_ctr)
-        self._arena = None
         # True: BatchNorm-apply + ReLU folded into every conv's operand read (no activated
         # tensor in HBM).  False: one HBM-bound pass writes the activated tensor and the convs
         # run their plain (faster) MFMA loop.  Measured on MI355X: see DESIGN.md §4.
@@ -166,7 +136,6 @@ class ResNet(nn.Module):
         self.fuse_bn_stats = os.environ.get("AIR_BN_STATS", "1") == "1"
         # weight gradients on a side HIP stream, overlapping the HBM-bound BN-backward passes
         self.overlap_wgrad = os.environ.get("AIR_OVERLAP_WGRAD", "1") == "1"
-        self._side_stream = None
         # Winograd weight transforms (a ~9 us kernel in front of each of the 16 + 16 forward / dgrad launches of the
         # 3x3 stride-1 layers) depend on the weights only: from the second training step on they run on the side
         # stream at the start of the step, under the front-end and the first layers (ops.conv2d_prepack)
@@ -174,30 +143,13 @@ class ResNet(nn.Module):
         self._geo = {}    # layer key -> (input shape, stride, padding) seen by the last training forward
         self._packs = {}  # (layer key, pass) -> persistent buffer
         self._pack_ev = [None, None]
-        self._bucketer = None  # dist.GradBucketer when the all-reduce is overlapped with backward
-
-    def enable_ddp_overlap(self, bucket_bytes=None):
-        """Launch the gradient all-reduce from inside backward (one process per GPU, world size > 1)."""
-        from .dist import GradBucketer
-        self._bucketer = GradBucketer(bucket_bytes)
-        return self
 
     def __getstate__(self):
-        """Whole-module pickles (main_train.py:675-704 -> generate_score.py:46-48): the flat arenas, the
-        side stream and an installed noise tensor are runtime state and are rebuilt on first use."""
-        st = dict(self.__dict__)
-        st["_arena"] = None
-        st["_side_stream"] = None
+        """Also runtime state: the prepacked weights and an installed noise tensor."""
+        st = super().__getstate__()
         st["_geo"], st["_packs"], st["_pack_ev"] = {}, {}, [None, None]
-        st["_bucketer"] = None
-        st["_segment_cut"] = None
         st["_noise_tensor"] = None
-        if st.get("_noise_ctr") is not None:  # the device-side counter travels as its value
-            st["_noise_offset"] = int(st["_noise_ctr"].item())
-        st["_noise_ctr"] = None
-        st["_noise_ctrs"] = None
-        st.pop("_last_saved_for_test", None)
-        st.pop("keep_saved_for_test", None)
+        self.fold_counter(st, "_noise")
         if st.get("noise_mode") == "tensor":
             st["noise_mode"] = "device"
         return st
@@ -231,16 +183,6 @@ class ResNet(nn.Module):
             for blk in layer:
                 yield blk
 
-    def arena(self):
-        """Flat parameter/gradient arenas (built lazily, rebuilt after .to(device))."""
-        dev = self.conv1.weight.device
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()),
-                                     tail_names=("fc_mu.weight", "fc_mu.bias"))
-        if not self._arena.bound() or self._arena.device != dev:
-            self._arena.bind(dev)
-        return self._arena
-
     def set_attention_noise(self, noise):
         """Install the (B, T', 256) noise tensor to use (already scaled), or None."""
         self._noise_tensor = noise
@@ -254,32 +196,11 @@ class ResNet(nn.Module):
             if tuple(n.shape) != (B, T, 256):
                 raise _hip.AirError("attention noise must be (B, T', 256), got %s" % (tuple(n.shape),))
             return n.to(device).contiguous()
-        # (seed, offset) of the Philox stream: the offset lives on the device and the draw advances it there, so
-        # that a step captured in a hipGraph draws fresh noise on every replay (resnet.py:38 draws per call) and
-        # eager launches and replays walk one sequence
-        # ONE counter per device, never replaced once made: a captured hipGraph (train.Trainer, GraphedScorer) holds
-        # its address.  Moving to another device first folds the live count back into the host field, so that the
-        # Philox sequence goes on instead of restarting (it restarted from the stale host value).
-        ctrs = getattr(self, "_noise_ctrs", None)
-        if ctrs is None:
-            ctrs = self._noise_ctrs = {}
-        ctr = ctrs.get(device)
-        if ctr is None:
-            live = getattr(self, "_noise_ctr", None)
-            if live is not None:
-                self._noise_offset = int(live.item())
-            ctr = ctrs[device] = torch.tensor([self._noise_offset], dtype=torch.int64, device=device)
-        elif getattr(self, "_noise_ctr", None) is not ctr:
-            # back on a device used before: carry the count of the counter used in between over (device-side copy)
-            live = getattr(self, "_noise_ctr", None)
-            if live is not None:
-                ctr.copy_(live)
-        self._noise_ctr = ctr
+        # resnet.py:38 draws per call: the Philox offset lives on the device and the draw advances it there
+        ctr = self.device_counter("_noise", device)
         return ops.randn_ctr((B, T, 256), device, self._noise_seed, ctr, self.noise_scale)
 
-    def forward(self, x):
-        if not x.is_cuda:
-            raise _hip.AirError("ResNet HIP path needs a GPU tensor; there is no CPU fallback")
+    def check_input(self, x):
         if x.dim() != 4 or x.shape[1] != 1:
             raise ValueError("ResNet expects (B, 1, F, T), got %s" % (tuple(x.shape),))
         if x.shape[0] == 1 and self.training:
@@ -293,30 +214,6 @@ class ResNet(nn.Module):
             # any length, resnet.py:23-46) take its in-place variant, whose per-frame vectors still live in LDS
             raise ValueError("ResNet HIP path: %d input frames give %d pooled frames; the SelfAttention pooling "
                              "kernels hold at most %d" % (x.shape[3], ta, self.MAX_POOL_FRAMES_GLOBAL))
-        x = x.float().contiguous()  # main_train.py:338 hands over a transposed view
-        arena = self.arena()
-        # eval-mode forward never records a graph (backward through running-stat BN is not
-        # on the hot path; generate_score.py only scores)
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for _, p, _, _ in arena.entries):
-            params = [p for _, p, _, _ in arena.entries]
-            return _ResNetFn.apply(self, x, None, *params)
-        feat, mu, _ = self._forward_impl(x, None, save=False)
-        return feat, mu
-
-    def forward_saved(self, x):
-        """The train-mode forward WITHOUT autograd: (feat, saved).  With ``backward_saved`` this is what
-        ``_ResNetFn`` does, callable from one Python thread - train.Trainer captures the step as several hipGraphs cut
-        between backward's bucket boundaries (autograd would run backward on its own worker thread)."""
-        x = x.float().contiguous()
-        self.arena()
-        feat, mu, saved = self._forward_impl(x, None, save=True)
-        saved["logits"] = mu  # the CE head's input (train.Trainer, add_loss=None)
-        return feat, saved
-
-    def backward_saved(self, saved, dfeat, dout=None):
-        """Gradients of every arena entry (views of the gradient arena, None where there is none), in arena order.
-        dout: the gradient of saved["logits"] (the CE head), or None."""
-        return self._backward_impl(saved, dfeat, dout)
 
     def _launch_prepack(self, fuse):
         """Enqueue the weight transforms of every conv behind conv1 - Winograd for the 3x3 stride-1 layers, the direct
@@ -385,12 +282,13 @@ class ResNet(nn.Module):
         return live
 
     # ------------------------------------------------------------------ forward
-    def _forward_impl(self, x, noise, save):
+    def _forward_impl(self, x, noise=None, save=False):
+        """noise: the attention noise to use instead of this model's draw (tests)."""
         training = self.training
         S = {} if save else None
         w = lambda conv: conv.weight.detach()
         c1 = ops.conv2d_fwd(x, w(self.conv1), (3, 1), (1, 1))  # resnet.py:176
-        st1 = _bn_train_coeffs(c1, self.bn1, training)
+        st1 = ops.bn_coeffs(c1, self.bn1, training)
         cur = ops.bn_apply(c1, st1[2], st1[3], relu=True)  # resnet.py:177
         if save:
             S["x"], S["c1"], S["st1"] = x, c1, st1
@@ -426,7 +324,7 @@ class ResNet(nn.Module):
         for bi, blk in enumerate(blocks):
             s = blk.stride
             self._geo_sp[(bi, 1)], self._geo_sp[(bi, 2)], self._geo_sp[(bi, 0)] = (s, 1), (1, 1), (s, 0)
-            stA = _bn_train_coeffs(cur, blk.bn1, training, cur_rec)
+            stA = ops.bn_coeffs(cur, blk.bn1, training, cur_rec)
             if fuse:  # BN-apply + ReLU folded into the conv's operand read (no activated tensor)
                 actA, pA = cur, dict(in_scale=stA[2], in_shift=stA[3], relu=True)
             else:     # activated tensor written once (HBM-bound pass), convs run their plain loop
@@ -443,7 +341,7 @@ class ResNet(nn.Module):
                 else:
                     sc = cur
                 h, h_rec = conv_st(want_stats, actA, w(blk.conv1), s, 1, w_packed=packed((bi, 1), 0, actA.shape), **pA)
-            stB = _bn_train_coeffs(h, blk.bn2, training, h_rec)
+            stB = ops.bn_coeffs(h, blk.bn2, training, h_rec)
             if fuse:
                 actB, pB = h, dict(in_scale=stB[2], in_shift=stB[3], relu=True)
             else:
@@ -456,7 +354,7 @@ class ResNet(nn.Module):
             cur = out
         self._geo_sp[(-1, 5)] = (1, (0, 1))
         c5 = ops.conv2d_fwd(cur, w(self.conv5), 1, (0, 1), w_packed=packed((-1, 5), 0, cur.shape))  # resnet.py:182
-        st5 = _bn_train_coeffs(c5, self.bn5, training)
+        st5 = ops.bn_coeffs(c5, self.bn5, training)
         a5 = ops.bn_apply(c5, st5[2], st5[3], relu=True)  # resnet.py:183
         B, C5, H5, T5 = a5.shape
         if H5 != 1:
@@ -483,14 +381,8 @@ class ResNet(nn.Module):
     def _backward_impl(self, S, dfeat, dmu):
         arena = self.arena()
         # weight gradients on the side stream (schedule.py), an accumulating pass included
-        sch = BackwardSchedule(self, arena, self.overlap_wgrad, getattr(self, "_bucketer", None), side_when_accumulating=True)
-        G, main = sch.G, sch.main
-        have = set()
-
-        def gv(mod_name):
-            have.add(mod_name)
-            return G[mod_name]
-
+        sch = BackwardSchedule(self, arena, self.overlap_wgrad, self._bucketer, side_when_accumulating=True)
+        gv, main = sch.grad, sch.main
         names = {id(p): n for n, p in self.named_parameters()}
         nm = lambda p: names[id(p)]
         w = lambda conv: conv.weight.detach()
@@ -585,4 +477,4 @@ class ResNet(nn.Module):
                                dgamma=gv("bn1.weight"), dbeta=gv("bn1.bias"))
         gc1 = gv("conv1.weight")
         sch.on_side(lambda: ops.conv2d_wgrad(S["x"], dc1, self.conv1.weight.shape, (3, 1), (1, 1), out=gc1), dc1)
-        return sch.finish(have.__contains__, "fc_mu.weight" in have)
+        return sch.finish()

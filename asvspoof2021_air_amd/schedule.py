@@ -1,12 +1,13 @@
-"""The stream schedule shared by the backward passes (ResNet, Res2Net2's fp32 and bf16-resident paths).
+"""The stream schedule shared by the backward passes of every hip_model.HipModel (ResNet, Res2Net2's fp32 and
+bf16-resident paths, LCNN, Res2Net).
 
 Weight gradients feed nothing until the optimiser, so they may run on a SIDE stream: the MFMA-bound weight-gradient
 kernels overlap the HBM-bound BatchNorm-backward passes and the dgrad chain of the main stream.  Ordering: a weight
 gradient starts after an event of the main stream that marks its operands ready; the tensors it reads are kept alive
 until the join (the caching allocator would hand their memory back to the main stream); the main stream joins the side
 stream before the gradients are used.  The schedule also reports where a part of the gradient arena is final (a
-segment cut of train.Trainer's hipGraph capture, a bucket of dist.GradBucketer) and folds an accumulating backward
-back into the old sums."""
+segment cut of train.Trainer's hipGraph capture, a bucket of dist.GradBucketer), records which gradients a pass wrote
+and folds an accumulating backward back into the old sums."""
 import torch
 
 from . import ops
@@ -34,10 +35,16 @@ class BackwardSchedule:
         self.main = torch.cuda.current_stream()
         self.side = side_stream(model) if self.use_side else self.main
         self.keep = []  # tensors the side stream reads
-        self.cut = getattr(model, "_segment_cut", None)
+        self.cut = model._segment_cut
+        self.have = set()  # names handed out by grad()
         self.bucketer = None if self.accumulating else bucketer
         if self.bucketer is not None:
             self.bucketer.reset(arena.grad, arena.head_total)
+
+    def grad(self, name):
+        """The gradient-arena view of parameter ``name``, for a kernel to write; recorded as written for finish()."""
+        self.have.add(name)
+        return self.G[name]
 
     def on_side(self, fn, *reads, done=False):
         """Run fn() on the side stream once everything enqueued on main so far is done (inline without one).
@@ -76,13 +83,17 @@ class BackwardSchedule:
             self.main.wait_stream(self.side)  # every weight gradient is in the arena
         self.keep.clear()
 
-    def finish(self, has_grad, tail_has_grad, keep_old_tail=False):
+    def finish(self, has_grad=None, tail_has_grad=None, keep_old_tail=False):
         """Join, set arena.tail_has_grad and fold an accumulating pass's old sums back in.  Returns the gradients for
         autograd in arena order: None where has_grad(name) is False or where p.grad already is the arena view.
+        Without arguments: what grad() recorded (the tail has gradients when one of its names was handed out); a pass
+        that indexes G itself says which entries it wrote.
         keep_old_tail: an accumulating pass marks the tail live (its old sums), zeroing it first where this pass wrote
         none of it."""
         self.join()
         arena = self.arena
+        if has_grad is None:
+            has_grad, tail_has_grad = self.have.__contains__, not self.have.isdisjoint(arena.tail_names)
         arena.tail_has_grad = tail_has_grad
         if self.accumulating:
             if keep_old_tail:

@@ -20,6 +20,7 @@ import torch.distributed as td
 
 from . import dist as air_dist
 from .feature_extraction import LFCC
+from .hip_model import HipModel
 from .loss import AngularIsoLoss, IsolateLoss, IsolateSquareLoss, P2SGradLoss
 from .optim import FusedAdam, FusedSGD
 
@@ -324,11 +325,7 @@ class Trainer:
         communication stream between two replays, underneath the next segment: replay's 0.2 - 0.4 ms of host time per
         step AND BASELINE configs[3]'s "all-reduce overlapped with backward".  Same kernels in the same order as the
         one-chain capture and as the eager step: bit-identical (tests/test_dist_gpu.py)."""
-        from .ecapa_tdnn import Res2Net2
-        from .lcnn import LCNN
-        from .res2net import Res2Net
-        from .resnet import ResNet
-        self.use_graph = bool(on) and isinstance(self.model, (Res2Net2, ResNet, LCNN, Res2Net))
+        self.use_graph = bool(on) and isinstance(self.model, HipModel)
         if segments is None:
             env = os.environ.get("AIR_GRAPH_SEGMENTS", "")
             segments = (env == "1") if env in ("0", "1") else self.world > 1

@@ -11,7 +11,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 
 from asvspoof2021_air_amd import dist as air_dist
-from asvspoof2021_air_amd.arena import ParamArena
+from asvspoof2021_air_amd.hip_model import HipModel
 
 
 def test_bucket_slices_cover_reverse_order():
@@ -23,19 +23,13 @@ def test_bucket_slices_cover_reverse_order():
     assert air_dist.bucket_slices(10, 16) == [(6, 10), (2, 6), (0, 2)]
 
 
-class Toy(nn.Module):
+class Toy(HipModel):
+    TAIL = ("tail.weight", "tail.bias")
+
     def __init__(self):
         super().__init__()
         self.a = nn.Linear(7, 5)
         self.tail = nn.Linear(5, 2)
-        self._arena = None
-
-    def arena(self):
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()), tail_names=("tail.weight", "tail.bias"))
-        if not self._arena.bound():
-            self._arena.bind(self.a.weight.device)
-        return self._arena
 
 
 def test_arena_views_and_tail():
@@ -117,8 +111,9 @@ def test_allreduce_grads_gloo_world2():
     assert dict(out) == {0: True, 1: True}
 
 
-class Toy8(nn.Module):
+class Toy8(HipModel):
     """Several tensors of awkward sizes so that small buckets cut through the middle of them."""
+    TAIL = ("tail.weight", "tail.bias")
 
     def __init__(self):
         super().__init__()
@@ -126,14 +121,6 @@ class Toy8(nn.Module):
         self.b = nn.Linear(11, 9)
         self.c = nn.Linear(9, 7)
         self.tail = nn.Linear(7, 3)
-        self._arena = None
-
-    def arena(self):
-        if self._arena is None:
-            self._arena = ParamArena(list(self.named_parameters()), tail_names=("tail.weight", "tail.bias"))
-        if not self._arena.bound():
-            self._arena.bind(self.a.weight.device)
-        return self._arena
 
 
 def _worker8(rank, world, port, out, tail_has_grad):

@@ -285,7 +285,10 @@ class AdversarialTrainer(Trainer):
         self.last = {"adv_loss": None if adv is None else adv.detach(), "classifier_loss": closs}
         return loss.detach(), neg_scores
 
-    def step(self, pcm, labels, channels=None, start=None, epoch_num=1):
-        if self.augment is not None:
-            pcm = self.augment(pcm)
-        return self.step_features(self.features(pcm, start), labels, channels, epoch_num)
+    def step(self, pcm, labels, channels=None, start=None, epoch_num=1, lengths=None):
+        """``lengths``: int32 (B,), a ragged batch as in ``Trainer.step`` (eager: this step is not captured)."""
+        self._refuse_ragged_augment(lengths)
+        if lengths is not None and self.augment is not None:
+            lengths = self._ragged_lengths(lengths, pcm)
+        pcm = self._augment(pcm, lengths)
+        return self.step_features(self.features(pcm, start, lengths), labels, channels, epoch_num)

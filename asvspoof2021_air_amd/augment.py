@@ -47,25 +47,58 @@ def synthetic_ir_bank(n_device=27, n_space=3, taps=1024, sr=16000, seed=688):
     return torch.from_numpy(bank.astype(np.float32))
 
 
-def ir_convolve(pcm, irs, idx=None, normalize=True, out=None):
-    """pcm (B, L) fp32 GPU, irs (n_ir, H) fp32 GPU, idx (B,) int32 GPU or None -> (B, L)."""
+def _device_lengths(lengths, B, Lcap, device):
+    """``lengths`` as the int32 (B,) device tensor the ragged kernel reads: a GPU tensor is used as is (the kernel clamps
+    it to [1, Lcap]), a host tensor or sequence is checked (ValueError) and uploaded, as ``LFCC.forward_ragged`` does."""
+    if not (torch.is_tensor(lengths) and lengths.is_cuda):
+        host = torch.as_tensor(lengths).reshape(-1)
+        if host.numel() != B or host.is_floating_point() or host.dtype == torch.bool:
+            raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
+        if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
+            raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
+                Lcap, int(host.min()), int(host.max())))
+        lengths = host.to(torch.int32).to(device)
+    elif lengths.numel() != B:
+        raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
+    return lengths.to(torch.int32).contiguous()  # (no-op for what the dataset hands over)
+
+
+def ir_convolve(pcm, irs, idx=None, normalize=True, out=None, lengths=None):
+    """pcm (B, L) fp32 GPU, irs (n_ir, H) fp32 GPU, idx (B,) int32 GPU or None -> (B, L).
+
+    ``lengths`` (B,) int32: a ragged batch in one launch (``air_ir_convolve_ragged``) - row b of ``pcm`` (B, Lcap), fp32
+    or int16 (s / 32768), holds lengths[b] samples; what follows them is never read.  Row b of the fp32 result is, bit
+    for bit, what the dense call gives for that utterance alone (convolved, truncated and peak-normalised over its own
+    samples), followed by zeros.  A GPU tensor is used as is, host values are checked (ValueError) and uploaded."""
     if not pcm.is_cuda or not irs.is_cuda:
         raise _hip.AirError("ir_convolve needs GPU tensors; there is no CPU fallback")
     B, L = pcm.shape
     n_ir, H = irs.shape
-    y = out if out is not None else torch.empty_like(pcm)
+    if lengths is not None:
+        lengths = _device_lengths(lengths, B, L, pcm.device)
+        if pcm.dtype not in (torch.float32, torch.int16):
+            raise _hip.AirError("a ragged batch is float32 or int16, got %s" % pcm.dtype)
+    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
     lib = _hip.lib()
     n = lib.air_ir_convolve_ws_bytes_ex(_hip.ci(B), _hip.ci(n_ir), _hip.ci(H))  # (+ the FFT tables when H qualifies)
     ws = ops.workspace(n, pcm.device)
-    _hip.check(lib.air_ir_convolve(_hip.dptr(pcm), _hip.ci(B), _hip.ci(L), _hip.dptr(irs), _hip.ci(n_ir),
-                                   _hip.ci(H), _hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0),
-                                   _hip.dptr(y), _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream()),
-               "air_ir_convolve")
+    tail = (_hip.dptr(irs), _hip.ci(n_ir), _hip.ci(H), _hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0),
+            _hip.dptr(y), _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream())
+    if lengths is None:
+        _hip.check(lib.air_ir_convolve(_hip.dptr(pcm), _hip.ci(B), _hip.ci(L), *tail), "air_ir_convolve")
+    else:
+        i16 = pcm.dtype == torch.int16
+        null = _hip.dptr(None, allow_none=True)
+        _hip.check(lib.air_ir_convolve_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
+                                              _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32), *tail),
+                   "air_ir_convolve_ragged")
     return y
 
 
 class ChannelAugment:
     """Per-utterance random IR from a bank, applied with probability ``p``."""
+
+    supports_lengths = True  # __call__(pcm, lengths=...) augments a ragged batch over each row's own samples (Trainer.step)
 
     def __init__(self, irs=None, p=1.0, seed=688, normalize=True, device="cuda"):
         self.irs = (irs if irs is not None else synthetic_ir_bank()).to(device=device, dtype=torch.float32).contiguous()
@@ -81,7 +114,10 @@ class ChannelAugment:
             idx[self.rng.random(batch) >= self.p] = -1
         return idx
 
-    def __call__(self, pcm, idx=None):
+    def __call__(self, pcm, idx=None, lengths=None):
+        """``lengths``: int32 (B,), a ragged batch (``ir_convolve``): fp32 or int16 in, fp32 out, the rows' tails zero."""
+        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
+            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
         if idx is None:
             idx = self.draw(pcm.shape[0])
         if not torch.is_tensor(idx):
@@ -97,4 +133,5 @@ class ChannelAugment:
             idx = slot[0].to(pcm.device, non_blocking=True)
             slot[1] = torch.cuda.Event()
             slot[1].record()
-        return ir_convolve(pcm, self.irs, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), self.normalize)
+        return ir_convolve(pcm, self.irs, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), self.normalize,
+                           lengths=lengths)

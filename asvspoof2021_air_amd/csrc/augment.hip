@@ -26,6 +26,14 @@
 // inverse passes run the other way round, so nothing is ever re-ordered; the first pass reads PCM straight from
 // global memory and the last one writes y straight to it.  Same result as the direct form to fp32 FFT rounding
 // (~3e-7 of the output scale; tests/test_augment.py holds both to the same bound).
+//
+// Ragged batches (air_ir_convolve_ragged): the same two kernels, templated on the sample type (fp32, or 16-bit PCM
+// converted as s / 32768 while it is staged) and given the row capacity Lcap plus the per-row lengths in device memory.
+// Row b is convolved, peak-measured and rescaled over its own L_b = clamp(lengths[b], 1, Lcap) samples only: L_b takes
+// the place of L in the staging clamp and at the store, nothing inside the FMA / butterfly loops knows about it, so
+// y[b, :L_b] carries the bits of the dense call on that utterance alone.  [L_b, Lcap) is written as zero; a workgroup
+// whose outputs all lie there stores its zeros and returns.  The dense entry point launches the fp32 instantiation
+// without lengths (L_b = Lcap = L).
 #include "air_common.h"
 #include "air_fft16.h"
 #include "air_options.h"
@@ -40,19 +48,35 @@ __device__ __forceinline__ void atomic_max_pos(unsigned* p, float v) {
   atomicMax(p, __float_as_uint(v));  // v >= 0: unsigned order == float order
 }
 
-__global__ __launch_bounds__(FIR_NT) void fir_kernel(const float* __restrict__ x, int L,
+__device__ __forceinline__ float ir_sample(const float* __restrict__ p, int i) { return p[i]; }
+__device__ __forceinline__ float ir_sample(const short* __restrict__ p, int i) { return (float)p[i] * (1.0f / 32768.0f); }  // exact
+
+// samples of row b: its length from device memory, kept inside the row (ragged), or the whole row (lengths NULL)
+__device__ __forceinline__ int ir_row_len(const int* __restrict__ lengths, int b, int Lcap) {
+  return lengths ? min(max(lengths[b], 1), Lcap) : Lcap;
+}
+
+// y[n0 + i] = x[n0 + i] for n0 + i < L, 0 up to Lcap (i < span): pass-through rows, and with n0 >= L the dead tail
+template <typename T>
+__device__ __forceinline__ void ir_copy_span(const T* __restrict__ xb, float* __restrict__ yb, int n0, int span, int L, int Lcap,
+                                             int t, int nt) {
+  for (int n = n0 + t; n < min(n0 + span, Lcap); n += nt) yb[n] = n < L ? ir_sample(xb, n) : 0.0f;
+}
+
+template <typename T>
+__global__ __launch_bounds__(FIR_NT) void fir_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
                                                      const float* __restrict__ irs, int H,
                                                      const int* __restrict__ idx, float* __restrict__ y,
                                                      unsigned* __restrict__ peaks, int n_ir) {
   __shared__ __attribute__((aligned(16))) float xs[FIR_GROUPS * FIR_GS];
   __shared__ __attribute__((aligned(16))) float hs[FIR_KC];
   const int b = blockIdx.y, n0 = blockIdx.x * FIR_BLK, t = threadIdx.x;
-  const float* __restrict__ xb = x + (size_t)b * L;
-  float* __restrict__ yb = y + (size_t)b * L;
+  const int L = ir_row_len(lengths, b, Lcap);
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
   const int ir = idx ? min(idx[b], n_ir - 1) : 0;  // indices are caller data: never read past the IR table
-  if (ir < 0) {  // pass-through utterance
-    for (int i = t; i < FIR_BLK; i += FIR_NT)
-      if (n0 + i < L) yb[n0 + i] = xb[n0 + i];
+  if (ir < 0 || n0 >= L) {  // pass-through utterance, or a block wholly behind the row's length: zeros
+    ir_copy_span(xb, yb, n0, FIR_BLK, L, Lcap, t, FIR_NT);
     return;
   }
   const float* __restrict__ hb = irs + (size_t)ir * H;
@@ -67,7 +91,7 @@ __global__ __launch_bounds__(FIR_NT) void fir_kernel(const float* __restrict__ x
     const int m0 = n0 - kc - (FIR_KC - 1);
     for (int p = t; p < FIR_GROUPS * 8; p += FIR_NT) {
       const int m = m0 + p;
-      const float v = (m >= 0 && m < L) ? xb[m] : 0.0f;
+      const float v = (m >= 0 && m < L) ? ir_sample(xb, m) : 0.0f;
       xs[(p >> 3) * FIR_GS + (p & 7)] = v;
       if (kc == 0 && p >= FIR_KC - 1) xpeak = fmaxf(xpeak, fabsf(v));  // this block's own samples
     }
@@ -108,6 +132,8 @@ __global__ __launch_bounds__(FIR_NT) void fir_kernel(const float* __restrict__ x
     if (n < L) {
       yb[n] = out[r];
       ypeak = fmaxf(ypeak, fabsf(out[r]));
+    } else if (n < Lcap) {
+      yb[n] = 0.0f;
     }
   }
   if (peaks) {
@@ -120,15 +146,16 @@ __global__ __launch_bounds__(FIR_NT) void fir_kernel(const float* __restrict__ x
   }
 }
 
-// y_b *= max|x_b| / max|y_b|  (augmented utterances only)
-__global__ __launch_bounds__(256) void fir_rescale_kernel(float* __restrict__ y, int L, const int* __restrict__ idx,
-                                                          const unsigned* __restrict__ peaks) {
+// y_b *= max|x_b| / max|y_b|  (augmented utterances only; the row's own samples only)
+__global__ __launch_bounds__(256) void fir_rescale_kernel(float* __restrict__ y, int Lcap, const int* __restrict__ lengths,
+                                                          const int* __restrict__ idx, const unsigned* __restrict__ peaks) {
   const int b = blockIdx.y;
   if (idx && idx[b] < 0) return;
   const float px = __uint_as_float(peaks[2 * b]), py = __uint_as_float(peaks[2 * b + 1]);
   if (!(py > 0.0f)) return;
   const float g = px / py;
-  float* __restrict__ yb = y + (size_t)b * L;
+  const int L = ir_row_len(lengths, b, Lcap);
+  float* __restrict__ yb = y + (size_t)b * Lcap;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < L; i += gridDim.x * 256) yb[i] *= g;
 }
 
@@ -229,17 +256,20 @@ __global__ __launch_bounds__(FC_NT) void fc_spectrum_kernel(const float* __restr
 }
 
 // blockIdx.x = pair of output blocks (2 p, 2 p + 1) of utterance blockIdx.y
-__global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const float* __restrict__ x, int L, const cf* __restrict__ spec,
-                                                            const cf* __restrict__ tw, const int* __restrict__ idx,
-                                                            float* __restrict__ y, unsigned* __restrict__ peaks, int n_ir) {
+template <typename T>
+__global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                            const cf* __restrict__ spec, const cf* __restrict__ tw,
+                                                            const int* __restrict__ idx, float* __restrict__ y,
+                                                            unsigned* __restrict__ peaks, int n_ir) {
   __shared__ cf buf[FC_LDS];
   const int b = blockIdx.y, t = threadIdx.x;
-  const float* __restrict__ xb = x + (size_t)b * L;
-  float* __restrict__ yb = y + (size_t)b * L;
+  const int L = ir_row_len(lengths, b, Lcap);
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
   const int baseA = 2 * blockIdx.x * FC_V, baseB = baseA + FC_V;  // first output sample of either block
   const int ir = idx ? min(idx[b], n_ir - 1) : 0;
-  if (ir < 0) {  // pass-through utterance
-    for (int i = baseA + t; i < min(baseA + 2 * FC_V, L); i += FC_NT) yb[i] = xb[i];
+  if (ir < 0 || baseA >= L) {  // pass-through utterance, or a pair wholly behind the row's length: zeros
+    ir_copy_span(xb, yb, baseA, 2 * FC_V, L, Lcap, t, FC_NT);
     return;
   }
   cf v[16];
@@ -247,8 +277,8 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const float* __restr
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int mA = baseA - FC_OV + 256 * j + t, mB = mA + FC_V;
-    const float a = (mA >= 0 && mA < L) ? xb[mA] : 0.0f;
-    const float c = mB < L ? xb[mB] : 0.0f;
+    const float a = (mA >= 0 && mA < L) ? ir_sample(xb, mA) : 0.0f;
+    const float c = mB < L ? ir_sample(xb, mB) : 0.0f;
     v[j] = cf{a, c};
     if (j >= FC_OV / 256) xpeak = fmaxf(xpeak, fmaxf(fabsf(a), fabsf(c)));  // the blocks' own samples
   }
@@ -264,10 +294,14 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const float* __restr
     if (baseA + o < L) {
       yb[baseA + o] = v[a][0];
       ypeak = fmaxf(ypeak, fabsf(v[a][0]));
+    } else if (baseA + o < Lcap) {
+      yb[baseA + o] = 0.0f;
     }
     if (baseB + o < L) {
       yb[baseB + o] = v[a][1];
       ypeak = fmaxf(ypeak, fabsf(v[a][1]));
+    } else if (baseB + o < Lcap) {
+      yb[baseB + o] = 0.0f;
     }
   }
   if (peaks) {
@@ -282,6 +316,38 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const float* __restr
 
 inline size_t fc_align(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool fc_wanted(int H) { return air_opt(AIR_OPT_IR_FFT) != 0 && H >= FC_MINH && H <= FC_MAXH; }
+
+// Both entry points, arguments already checked.  lengths NULL: every row holds L samples (the dense call).
+template <typename T>
+int ir_launch(const T* x, int B, int L, const int* lengths, const float* irs, int n_ir, int H, const int* ir_idx,
+              int normalize, float* y, void* ws, size_t ws_bytes, hipStream_t st) {
+  unsigned* peaks = normalize ? reinterpret_cast<unsigned*>(ws) : nullptr;
+  if (peaks && hipMemsetAsync(peaks, 0, (size_t)B * 2 * sizeof(unsigned), st) != hipSuccess) return AIR_ELAUNCH;
+  if (fc_wanted(H) && ws && ws_bytes >= air_ir_convolve_ws_bytes_ex(B, n_ir, H)) {
+    // (the tables are rebuilt per call - 16 + n_ir small workgroups - rather than cached against a bank the caller may
+    // rewrite in place)
+    char* base = reinterpret_cast<char*>(ws) + fc_align(air_ir_convolve_ws_bytes(B));
+    cf* tw = reinterpret_cast<cf*>(base);
+    cf* spec = reinterpret_cast<cf*>(base + fc_align((size_t)FC_N * sizeof(cf)));
+    hipLaunchKernelGGL(fc_twiddle_kernel, dim3(FC_N / 256), dim3(256), 0, st, tw);
+    AIR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(fc_spectrum_kernel, dim3(n_ir), dim3(FC_NT), 0, st, irs, H, tw, spec);
+    AIR_CHECK_LAUNCH();
+    const int nblk = (L + FC_V - 1) / FC_V;
+    hipLaunchKernelGGL(fc_convolve_kernel<T>, dim3((nblk + 1) / 2, B), dim3(FC_NT), 0, st, x, L, lengths, spec, tw, ir_idx, y,
+                       peaks, n_ir);
+    AIR_CHECK_LAUNCH();
+  } else {
+    const dim3 grid((L + FIR_BLK - 1) / FIR_BLK, B);
+    hipLaunchKernelGGL(fir_kernel<T>, grid, dim3(FIR_NT), 0, st, x, L, lengths, irs, H, ir_idx, y, peaks, n_ir);
+    AIR_CHECK_LAUNCH();
+  }
+  if (normalize) {
+    hipLaunchKernelGGL(fir_rescale_kernel, dim3(16, B), dim3(256), 0, st, y, L, lengths, ir_idx, peaks);
+    AIR_CHECK_LAUNCH();
+  }
+  return AIR_OK;
+}
 
 }  // namespace
 
@@ -300,32 +366,20 @@ int air_ir_convolve(const float* x, int B, int L, const float* irs, int n_ir, in
                     int normalize, float* y, void* ws, size_t ws_bytes, air_stream_t stream) {
   if (!x || !y || !irs || B <= 0 || L <= 0 || n_ir <= 0 || H <= 0 || x == y) return AIR_EINVAL;
   if (normalize && (!ws || ws_bytes < air_ir_convolve_ws_bytes(B))) return AIR_EWORKSPACE;
+  return ir_launch(x, B, L, nullptr, irs, n_ir, H, ir_idx, normalize, y, ws, ws_bytes, air_stream(stream));
+}
+
+int air_ir_convolve_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev,
+                           const float* irs, int n_ir, int H, const int* ir_idx, int normalize,
+                           float* y, void* ws, size_t ws_bytes, air_stream_t stream) {
+  if ((x != nullptr) == (x16 != nullptr) || !lengths_dev || !y || !irs || B <= 0 || Lcap <= 0 || n_ir <= 0 || H <= 0 ||
+      (x && x == y))
+    return AIR_EINVAL;
+  if (normalize && (!ws || ws_bytes < air_ir_convolve_ws_bytes(B))) return AIR_EWORKSPACE;
   hipStream_t st = air_stream(stream);
-  unsigned* peaks = normalize ? reinterpret_cast<unsigned*>(ws) : nullptr;
-  if (peaks && hipMemsetAsync(peaks, 0, (size_t)B * 2 * sizeof(unsigned), st) != hipSuccess) return AIR_ELAUNCH;
-  if (fc_wanted(H) && ws && ws_bytes >= air_ir_convolve_ws_bytes_ex(B, n_ir, H)) {
-    // (the tables are rebuilt per call - 16 + n_ir small workgroups - rather than cached against a bank the caller may
-    // rewrite in place)
-    char* base = reinterpret_cast<char*>(ws) + fc_align(air_ir_convolve_ws_bytes(B));
-    cf* tw = reinterpret_cast<cf*>(base);
-    cf* spec = reinterpret_cast<cf*>(base + fc_align((size_t)FC_N * sizeof(cf)));
-    hipLaunchKernelGGL(fc_twiddle_kernel, dim3(FC_N / 256), dim3(256), 0, st, tw);
-    AIR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fc_spectrum_kernel, dim3(n_ir), dim3(FC_NT), 0, st, irs, H, tw, spec);
-    AIR_CHECK_LAUNCH();
-    const int nblk = (L + FC_V - 1) / FC_V;
-    hipLaunchKernelGGL(fc_convolve_kernel, dim3((nblk + 1) / 2, B), dim3(FC_NT), 0, st, x, L, spec, tw, ir_idx, y, peaks, n_ir);
-    AIR_CHECK_LAUNCH();
-  } else {
-    const dim3 grid((L + FIR_BLK - 1) / FIR_BLK, B);
-    hipLaunchKernelGGL(fir_kernel, grid, dim3(FIR_NT), 0, st, x, L, irs, H, ir_idx, y, peaks, n_ir);
-    AIR_CHECK_LAUNCH();
-  }
-  if (normalize) {
-    hipLaunchKernelGGL(fir_rescale_kernel, dim3(16, B), dim3(256), 0, st, y, L, ir_idx, peaks);
-    AIR_CHECK_LAUNCH();
-  }
-  return AIR_OK;
+  if (x16)
+    return ir_launch(reinterpret_cast<const short*>(x16), B, Lcap, lengths_dev, irs, n_ir, H, ir_idx, normalize, y, ws, ws_bytes, st);
+  return ir_launch(x, B, Lcap, lengths_dev, irs, n_ir, H, ir_idx, normalize, y, ws, ws_bytes, st);
 }
 
 }  // extern "C"

@@ -225,15 +225,26 @@ class Trainer:
 
     def features(self, pcm, start=None, lengths=None):
         """(B, L) PCM -> model input, fused on the GPU (dataset.py:66-79 + main_train.py:338,:347).  ``lengths``: int32
-        (B,), the batch is ragged - row b of ``pcm`` holds lengths[b] samples (LFCC.forward_ragged)."""
+        (B,), the batch is ragged - row b of ``pcm`` holds lengths[b] samples (LFCC.forward_ragged).  Never augments (step does)."""
         if lengths is not None:
-            if self.augment is not None:
-                # the IR convolution normalises over the whole row: a ragged row would be scaled by its padding
-                raise NotImplementedError("ragged batches (lengths=...) are not supported together with augment")
+            self._refuse_ragged_augment(lengths)
             feat = self.lfcc.forward_ragged(pcm, lengths, self.feat_len, start, self.padding)
         else:
             feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, 60, feat_len)
         return feat if self.ecapa else feat.unsqueeze(1)
+
+    def _refuse_ragged_augment(self, lengths):
+        """A ragged batch needs an augment that is told the rows' lengths (``supports_lengths``: augment.ChannelAugment
+        convolves and peak-normalises each row over its own samples).  Any other - a plain callable of one argument -
+        would work over the whole row, and scale an utterance by, and convolve it into, its padding."""
+        if lengths is not None and self.augment is not None and not getattr(self.augment, "supports_lengths", False):
+            raise NotImplementedError("ragged batches (lengths=...) are not supported together with augment")
+
+    def _augment(self, pcm, lengths=None):
+        """The augmentation in front of the (captured) step; ragged: fp32 or int16 rows in, fp32 rows with zero tails out."""
+        if self.augment is None:
+            return pcm
+        return self.augment(pcm) if lengths is None else self.augment(pcm, lengths=lengths)
 
     def _head(self, feats, logits, labels):
         """The head's forward: (loss as logged, the loss backward() starts from, second output).  Second output:
@@ -295,11 +306,13 @@ class Trainer:
     def step(self, pcm, labels, start=None, lengths=None):
         """``lengths`` None: a batch of one length; a ``start`` forces the eager step.  ``lengths`` int32 (B,): a ragged
         batch - the crop offsets and the lengths are device data of the captured step, so it stays on hipGraph replay
-        with or without ``start``, and every batch of one (B, Lcap) shape replays the same capture."""
+        with or without ``start``, and every batch of one (B, Lcap) shape replays the same capture.  With an ``augment``
+        that takes lengths (ChannelAugment) the rows are augmented over their own samples in front of the captured region,
+        which then sees fp32 (B, Lcap) whatever the batch's dtype was."""
+        self._refuse_ragged_augment(lengths)
         if lengths is not None and self.augment is not None:
-            raise NotImplementedError("ragged batches (lengths=...) are not supported together with augment")
-        if self.augment is not None:
-            pcm = self.augment(pcm)
+            lengths = self._ragged_lengths(lengths, pcm)  # checked and uploaded once, for the augment and the front-end
+        pcm = self._augment(pcm, lengths)
         if self.use_graph and (start is None or lengths is not None):
             out = self._graphed_step(pcm, labels, lengths, start)
             if out is not None:

@@ -294,6 +294,22 @@ size_t air_ir_convolve_ws_bytes(int B);
 size_t air_ir_convolve_ws_bytes_ex(int B, int n_ir, int H);
 int air_ir_convolve(const float* x, int B, int L, const float* irs, int n_ir, int H, const int* ir_idx,
                     int normalize, float* y, void* ws, size_t ws_bytes, air_stream_t stream);
+/* Ragged batch: B rows of capacity Lcap (row b = x + b * Lcap), of which the first L_b = clamp(lengths_dev[b], 1, Lcap)
+ * samples are the utterance (the clamp only keeps a bad device value inside its row).  Exactly one of x (fp32) / x16
+ * (16-bit PCM, converted in the kernel as s / 32768, which is exact) is non-NULL.  y is fp32 (B, Lcap): y[b, :L_b] is
+ * exactly what air_ir_convolve writes for that utterance alone with L = L_b - the convolution truncated at L_b and, with
+ * normalize, max|x| and max|y| taken over [0, L_b) only - and y[b, L_b:] is written as 0.  ir_idx[b] < 0 copies
+ * x[b, :L_b] (converted, for x16) and zeroes the tail.  No input sample at index >= L_b is read.  The lengths are device
+ * data and nothing synchronises with the host, so the call can be captured in a graph.  The same kernels as the dense
+ * entry point (templated on the sample type, the row length taking the place of L at staging and at the store), the
+ * same route selection and the same workspace (air_ir_convolve_ws_bytes[_ex]): ONE convolution launch for the whole
+ * batch, its grid sized by Lcap, whose workgroups wholly behind L_b only write zeros and return; the rescale launch
+ * (normalize) and, on the FFT route, the two table launches as in the dense call.  A NULL lengths_dev, both or neither
+ * of x / x16, x == y or a non-positive size: AIR_EINVAL, ahead of any HIP call; normalize with a workspace below
+ * air_ir_convolve_ws_bytes(B): AIR_EWORKSPACE. */
+int air_ir_convolve_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev,
+                           const float* irs, int n_ir, int H, const int* ir_idx, int normalize,
+                           float* y, void* ws, size_t ws_bytes, air_stream_t stream);
 
 /* --------------------------------------------------------------- conv1d --
  * nn.Conv1d (stride 1) as used by ecapa_tdnn.py:39,46,55,111,118,140,143, with the

@@ -135,3 +135,152 @@ class ChannelAugment:
             slot[1].record()
         return ir_convolve(pcm, self.irs, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), self.normalize,
                            lengths=lengths)
+
+
+# ------------------------------------------------------------------------------------------------ transmission codec
+LAWS = ("ulaw", "alaw")  # air_g711_ragged's law indices
+
+
+def _lowpass64(ntaps, cutoff_hz, sr, beta):
+    """The float64 design behind ``codec_lowpass``."""
+    if ntaps < 1 or ntaps % 2 == 0:
+        raise ValueError("ntaps must be odd and positive, got %d" % ntaps)
+    fc = 2.0 * cutoff_hz / sr  # of Nyquist
+    n = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) / 2.0
+    h = fc * np.sinc(fc * n) * np.kaiser(ntaps, beta)
+    return h / h.sum()
+
+
+def codec_lowpass(ntaps=63, cutoff_hz=3680.0, sr=16000, beta=8.0):
+    """The low-pass both resamplers of ``g711_codec`` use: a Kaiser-windowed sinc of ``ntaps`` (odd) coefficients, cut
+    off at ``cutoff_hz`` of a ``sr`` Hz signal, unit DC gain.  Designed in float64 (numpy), returned as float32."""
+    return torch.from_numpy(_lowpass64(ntaps, cutoff_hz, sr, beta).astype(np.float32))
+
+
+def g711_codec(pcm, law_idx=None, lengths=None, fir=None, resample=True, normalize=True, out=None, return_codes=False):
+    """pcm (B, L) fp32 or int16 GPU -> (B, L) fp32: each row through a G.711 telephone channel (``air_g711_ragged``):
+    low-pass and decimate to half the rate, quantise to 16 bits, code and decode, interpolate back, rescale to the input
+    peak.  ``law_idx`` (B,) int32 GPU: 0 mu-law, 1 A-law, < 0 leaves the row unchanged; None is mu-law for all.
+    ``lengths`` as in ``ir_convolve``: row b holds lengths[b] samples, its tail is never read and comes back zero.
+    ``fir``: the low-pass (odd, at most 127 taps; default ``codec_lowpass()``).  ``resample=False`` codes every sample
+    at its own rate.  ``return_codes``: also the uint8 codes, (B, (L + 1) // 2) or, without resampling, (B, L)."""
+    if not pcm.is_cuda or (fir is not None and not fir.is_cuda) or (law_idx is not None and not law_idx.is_cuda):
+        raise _hip.AirError("g711_codec needs GPU tensors; there is no CPU fallback")
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
+    B, L = pcm.shape
+    if lengths is not None:
+        lengths = _device_lengths(lengths, B, L, pcm.device)
+    if law_idx is not None and law_idx.numel() != B:
+        raise ValueError("law_idx must have %d entries, got %d" % (B, law_idx.numel()))
+    if fir is None:
+        fir = _default_fir(pcm.device)
+    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
+    codes = torch.empty((B, (L + 1) // 2 if resample else L), dtype=torch.uint8, device=pcm.device) if return_codes else None
+    lib = _hip.lib()
+    n = lib.air_g711_ws_bytes(_hip.ci(B))
+    ws = ops.workspace(n, pcm.device)
+    i16 = pcm.dtype == torch.int16
+    null = _hip.dptr(None, allow_none=True)
+    _hip.check(lib.air_g711_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
+                                   _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True), _hip.dptr(fir),
+                                   _hip.ci(fir.numel()), _hip.dptr(law_idx, torch.int32, True), _hip.ci(1 if resample else 0),
+                                   _hip.ci(1 if normalize else 0), _hip.dptr(y), _hip.dptr(codes, torch.uint8, True),
+                                   _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream()), "air_g711_ragged")
+    return (y, codes) if return_codes else y
+
+
+_FIR = {}
+
+
+def _default_fir(device):
+    key = str(device)
+    if key not in _FIR:
+        _FIR[key] = codec_lowpass().to(device)
+    return _FIR[key]
+
+
+class CodecAugment:
+    """Per-utterance random G.711 law out of ``laws``, applied with probability ``p`` (the sample-parallel entries of the
+    reference's ``codec_landline`` list; channel_simulation/simulated_channel.py degrades the corpus with them offline)."""
+
+    supports_lengths = True
+
+    def __init__(self, laws=("ulaw", "alaw"), p=1.0, seed=688, normalize=True, fir=None, device="cuda"):
+        if not laws or any(name not in LAWS for name in laws):
+            raise ValueError("laws must be taken from %s, got %s" % (LAWS, laws))
+        self.laws = tuple(laws)
+        self._kernel_law = np.array([LAWS.index(name) for name in self.laws], dtype=np.int32)
+        self.p = float(p)
+        self.normalize = normalize
+        self.device = device
+        self.fir = None if fir is None else fir.to(device=device, dtype=torch.float32).contiguous()
+        self.rng = np.random.Generator(np.random.PCG64(seed))
+        self._pinned = {}
+
+    def draw(self, batch):
+        """(B,) int32 indices into ``laws``, -1 = leave the utterance unchanged."""
+        idx = self.rng.integers(0, len(self.laws), size=batch).astype(np.int32)
+        if self.p < 1.0:
+            idx[self.rng.random(batch) >= self.p] = -1
+        return idx
+
+    def __call__(self, pcm, idx=None, lengths=None):
+        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
+            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
+        if idx is None:
+            idx = self.draw(pcm.shape[0])
+        if not torch.is_tensor(idx):
+            idx = np.asarray(idx, dtype=np.int32)
+            idx = _upload_indices(self._pinned, np.where(idx < 0, -1, self._kernel_law[np.maximum(idx, 0)]).astype(np.int32),
+                                  pcm.device)
+        elif self.laws != LAWS:
+            raise ValueError("device indices are the kernel's own (0 mu-law, 1 A-law): pass host indices with laws=%s" % (self.laws,))
+        return g711_codec(pcm, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), lengths=lengths, fir=self.fir,
+                          normalize=self.normalize)
+
+
+def _upload_indices(pinned, idx, device):
+    """Asynchronous upload of a host int32 array from a pinned buffer kept per batch size (as ``ChannelAugment.__call__``:
+    a pageable copy would synchronise the stream)."""
+    slot = pinned.get(idx.size)
+    if slot is None:
+        slot = pinned[idx.size] = [torch.empty(idx.size, dtype=torch.int32).pin_memory(), None]
+    if slot[1] is not None:
+        slot[1].synchronize()  # the previous upload from this buffer has executed (one step of run-ahead)
+    slot[0].copy_(torch.from_numpy(idx))
+    dev = slot[0].to(device, non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    return dev
+
+
+class AugmentChain:
+    """Transmission codec, then recording device - the order of channel_simulation/simulated_device_channel.py:47-54.
+    Either stage may be None.  ``prepare(batch)`` draws for the next call and returns what was drawn as the channel
+    classes of ``AdversarialTrainer.step(..., channels=)``: 0 = unchanged (the reference's ``no_channel``), index + 1
+    otherwise; (B, 2) int64 (codec, device) with both stages, (B,) with one."""
+
+    supports_lengths = True
+
+    def __init__(self, codec=None, device=None):
+        if codec is None and device is None:
+            raise ValueError("AugmentChain needs a codec stage, a device stage, or both")
+        self.stages = [s for s in (codec, device) if s is not None]
+        self.codec, self.device = codec, device
+        self._prepared = None
+
+    def prepare(self, batch):
+        self._prepared = [np.asarray(s.draw(batch)) for s in self.stages]
+        labels = np.stack([np.where(i < 0, 0, i.astype(np.int64) + 1) for i in self._prepared], axis=1)
+        return torch.from_numpy(labels[:, 0].copy() if len(self.stages) == 1 else labels)
+
+    def __call__(self, pcm, lengths=None):
+        if lengths is not None:  # ahead of any draw
+            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
+        drawn, self._prepared = self._prepared, None
+        if drawn is not None and len(drawn[0]) != pcm.shape[0]:
+            raise ValueError("prepared for a batch of %d, called with %d" % (len(drawn[0]), pcm.shape[0]))
+        for k, stage in enumerate(self.stages):
+            pcm = stage(pcm, None if drawn is None else drawn[k], lengths=lengths)
+        return pcm

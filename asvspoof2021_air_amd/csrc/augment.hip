@@ -37,6 +37,7 @@
 #include "air_common.h"
 #include "air_fft16.h"
 #include "air_options.h"
+#include "g711.h"
 
 namespace {
 
@@ -349,6 +350,237 @@ int ir_launch(const T* x, int B, int L, const int* lengths, const float* irs, in
   return AIR_OK;
 }
 
+// ---- G.711 transmission codec (air_g711_ragged) ----------------------------------------------------------------------
+// 16 kHz -> low-pass, every second sample (8 kHz) -> 16-bit -> G.711 code -> 16-bit -> zero-stuff, low-pass -> 16 kHz, per
+// row over its own L_b samples (include/air_hip.h has the arithmetic).  A byte mover (4 or 2 bytes in, 4 out per sample),
+// so one workgroup takes a tile of GC_T outputs from global memory to global memory and keeps everything between in LDS:
+//   * it stages x[n0 - 2c - pc, n0 + GC_T + 2c) - its tile plus the halo of BOTH filters - split by parity into E / O:
+//     with the base chosen so that base + c is even, the even taps of the decimator read E and the odd taps O, both at
+//     unit stride;
+//   * it computes the GC_T / 2 + c 8 kHz samples its outputs need (the c of the halo are recomputed, not exchanged): a
+//     thread owns GC_VR = 5 consecutive ones (stride 5 over the lanes: no LDS bank is hit twice) behind two sliding
+//     register windows, one LDS read and GC_VR FMAs per tap, taps in ascending order into ONE accumulator; quantises,
+//     codes and decodes them (decode: a 256-entry table of d / 32768 in LDS) and leaves v in LDS;
+//   * it interpolates in polyphase form: a thread owns 8 consecutive outputs, the four whose (n + c) is even take the even
+//     taps and the other four the odd taps, off one sliding window of v - the stuffed zeros are never multiplied;
+//   * the outputs cross LDS once more so that the store is coalesced whatever Lcap's alignment.
+// Nothing in the arithmetic depends on Lcap or on the other rows, so row b of a ragged batch carries the bits of the call
+// on that utterance alone.
+constexpr int GC_NT = 256, GC_R = 8, GC_T = GC_NT * GC_R;  // outputs per workgroup
+constexpr int GC_MAXTAPS = 127, GC_MAXC = (GC_MAXTAPS - 1) / 2;
+constexpr int GC_VR = 5;       // 8 kHz samples per thread: GC_NT * GC_VR >= GC_T / 2 + GC_MAXC
+constexpr int GC_XH = 1168;    // floats per parity plane: >= GC_T / 2 + 2 GC_MAXC + GC_VR + 1; = 16 mod 32, so a wave's
+                               // staging stores (even lanes -> E, odd lanes -> O) fall on 32 different banks
+constexpr int GC_VS = 1104;    // v: one zero in front + GC_T / 2 + GC_MAXC samples, rounded up to whole threads
+static_assert(GC_XH >= GC_T / 2 + 2 * GC_MAXC + GC_VR + 1 && GC_XH % 32 == 16, "parity planes");
+static_assert(GC_VS >= 1 + GC_T / 2 + GC_MAXC + GC_VR && GC_NT * GC_VR >= GC_T / 2 + GC_MAXC, "8 kHz samples");
+static_assert(GC_T <= 2 * GC_XH && GC_NT == 256, "the outputs reuse the planes; one thread per table entry");
+
+__device__ __forceinline__ int g711_quantise(float u) {  // clamp(rint(u * 32768)): ties to even; NaN -> -32768
+  return (int)fminf(fmaxf(rintf(u * 32768.0f), -32768.0f), 32767.0f);
+}
+
+// the tile [n0, n0 + GC_T) of a row that is copied (pass-through) or lies behind its length: y, and zero codes
+template <typename T>
+__device__ __forceinline__ void g711_skip_tile(const T* __restrict__ xb, float* __restrict__ yb, unsigned char* __restrict__ cb,
+                                               int n0, int L, int Lcap, int c0, int cspan, int Ccap, int t) {
+  ir_copy_span(xb, yb, n0, GC_T, L, Lcap, t, GC_NT);
+  if (cb)
+    for (int m = c0 + t; m < min(c0 + cspan, Ccap); m += GC_NT) cb[m] = 0;
+}
+
+// PC = c & 1.  ae[r] -> y[nb + 2 r + PC] (even taps), ao[r] -> y[nb + 2 r + 1 - PC] (odd taps); w[i] = v at LDS index wb + i - j
+template <bool PC>
+__device__ __forceinline__ void g711_interp(const float* __restrict__ vs, const float* __restrict__ hs, int c, int wb,
+                                            float* __restrict__ o) {
+  float w[5], ae[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ao[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int i = 0; i < 5; ++i) w[i] = vs[wb + i];
+  for (int j = 0; j < c; ++j) {
+    const float he = hs[2 * j], ho = hs[2 * j + 1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ae[r] = fmaf(he, w[r + 1], ae[r]);
+      ao[r] = fmaf(ho, PC ? w[r] : w[r + 1], ao[r]);
+    }
+#pragma unroll
+    for (int i = 4; i > 0; --i) w[i] = w[i - 1];
+    w[0] = vs[wb - j - 1];
+  }
+  const float he = hs[2 * c];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    ae[r] = fmaf(he, w[r + 1], ae[r]);
+    o[2 * r + (PC ? 1 : 0)] = 2.0f * ae[r];
+    o[2 * r + (PC ? 0 : 1)] = 2.0f * ao[r];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(GC_NT) void g711_resample_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                              const float* __restrict__ fir, int ntaps,
+                                                              const int* __restrict__ law_idx, float* __restrict__ y,
+                                                              unsigned char* __restrict__ codes, unsigned* __restrict__ peaks) {
+  __shared__ __attribute__((aligned(16))) float xs[2 * GC_XH];  // E = xs, O = xs + GC_XH (O[-1] is read into a window slot that is never used)
+  __shared__ float vs[GC_VS];
+  __shared__ float hs[GC_MAXTAPS + 1];
+  __shared__ float dec[256];
+  const int b = blockIdx.y, n0 = blockIdx.x * GC_T, t = threadIdx.x;
+  const int L = ir_row_len(lengths, b, Lcap), M = (L + 1) >> 1, Mcap = (Lcap + 1) >> 1;
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
+  unsigned char* __restrict__ cb = codes ? codes + (size_t)b * Mcap : nullptr;
+  const int law = law_idx ? min(law_idx[b], 1) : 0;  // caller data: anything above 1 is A-law
+  if (law < 0 || n0 >= L) {
+    g711_skip_tile(xb, yb, cb, n0, L, Lcap, n0 >> 1, GC_T / 2, Mcap, t);
+    return;
+  }
+  const int c = (ntaps - 1) >> 1, pc = c & 1;
+  const int ib = n0 - 2 * c - pc;                 // first staged sample; ib + c is even
+  const int mbase = (n0 - c + pc) / 2;            // first 8 kHz sample of the tile (exact: the numerator is even)
+  const int D = (3 * c + pc - n0) / 2;            // tap 2 j of sample m reads E[m - j + D], tap 2 j + 1 O[m - j + D - 1]
+  const int NV = GC_T / 2 + c;
+  float xpeak = 0.0f;
+  for (int p = t; p < min(2 * GC_XH, GC_T + 4 * c + 12); p += GC_NT) {
+    const int i = ib + p;
+    const float v = (i >= 0 && i < L) ? ir_sample(xb, i) : 0.0f;
+    xs[(p & 1) * GC_XH + (p >> 1)] = v;
+    if (i >= n0 && i < n0 + GC_T) xpeak = fmaxf(xpeak, fabsf(v));  // this tile's own samples
+  }
+  if (t < ntaps) hs[t] = fir[t];
+  dec[t] = (float)g711_decode(law, t) * (1.0f / 32768.0f);
+  if (t == 0) vs[0] = 0.0f;
+  __syncthreads();
+
+  for (int jv = t * GC_VR; jv < NV; jv += GC_NT * GC_VR) {
+    const float* __restrict__ E = xs + (mbase + jv + D);
+    const float* __restrict__ O = E + GC_XH - 1;
+    float we[GC_VR], wo[GC_VR], u[GC_VR];
+#pragma unroll
+    for (int r = 0; r < GC_VR; ++r) {
+      we[r] = E[r];
+      wo[r] = O[r];
+      u[r] = 0.0f;
+    }
+    for (int j = 0; j < c; ++j) {
+      const float he = hs[2 * j], ho = hs[2 * j + 1];
+#pragma unroll
+      for (int r = 0; r < GC_VR; ++r) {
+        u[r] = fmaf(he, we[r], u[r]);
+        u[r] = fmaf(ho, wo[r], u[r]);
+      }
+#pragma unroll
+      for (int r = GC_VR - 1; r > 0; --r) {
+        we[r] = we[r - 1];
+        wo[r] = wo[r - 1];
+      }
+      we[0] = E[-j - 1];
+      wo[0] = O[-j - 1];
+    }
+    const float he = hs[2 * c];
+#pragma unroll
+    for (int r = 0; r < GC_VR; ++r) {
+      const int m = mbase + jv + r;
+      const bool live = m >= 0 && m < M;
+      const int code = g711_encode(law, g711_quantise(fmaf(he, we[r], u[r])));
+      vs[1 + jv + r] = live ? dec[code] : 0.0f;
+      if (cb && m >= (n0 >> 1) && m < (n0 >> 1) + GC_T / 2 && m < Mcap) cb[m] = live ? (unsigned char)code : 0;
+    }
+  }
+  __syncthreads();
+
+  float o[GC_R];
+  if (pc)
+    g711_interp<true>(vs, hs, c, 4 * t + c, o);
+  else
+    g711_interp<false>(vs, hs, c, 4 * t + c, o);
+  // (the planes were last read ahead of the barrier above)
+  reinterpret_cast<float4*>(xs)[2 * t] = make_float4(o[0], o[1], o[2], o[3]);
+  reinterpret_cast<float4*>(xs)[2 * t + 1] = make_float4(o[4], o[5], o[6], o[7]);
+  __syncthreads();
+  float ypeak = 0.0f;
+  for (int i = t; i < GC_T && n0 + i < Lcap; i += GC_NT) {
+    const float v = n0 + i < L ? xs[i] : 0.0f;
+    yb[n0 + i] = v;
+    ypeak = fmaxf(ypeak, fabsf(v));
+  }
+  if (peaks) {
+    xpeak = air_wave_max(xpeak);
+    ypeak = air_wave_max(ypeak);
+    if ((t & 63) == 0) {
+      atomic_max_pos(peaks + 2 * b, xpeak);
+      atomic_max_pos(peaks + 2 * b + 1, ypeak);
+    }
+  }
+}
+
+// resample = 0: every sample is quantised, coded and decoded at its own rate
+template <typename T>
+__global__ __launch_bounds__(GC_NT) void g711_code_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                          const int* __restrict__ law_idx, float* __restrict__ y,
+                                                          unsigned char* __restrict__ codes, unsigned* __restrict__ peaks) {
+  const int b = blockIdx.y, n0 = blockIdx.x * GC_T, t = threadIdx.x;
+  const int L = ir_row_len(lengths, b, Lcap);
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
+  unsigned char* __restrict__ cb = codes ? codes + (size_t)b * Lcap : nullptr;
+  const int law = law_idx ? min(law_idx[b], 1) : 0;
+  if (law < 0 || n0 >= L) {
+    g711_skip_tile(xb, yb, cb, n0, L, Lcap, n0, GC_T, Lcap, t);
+    return;
+  }
+  float xpeak = 0.0f, ypeak = 0.0f;
+  for (int n = n0 + t; n < min(n0 + GC_T, Lcap); n += GC_NT) {
+    float v = 0.0f;
+    int code = 0;
+    if (n < L) {
+      const float s = ir_sample(xb, n);
+      code = g711_encode(law, g711_quantise(s));
+      v = (float)g711_decode(law, code) * (1.0f / 32768.0f);
+      xpeak = fmaxf(xpeak, fabsf(s));
+      ypeak = fmaxf(ypeak, fabsf(v));
+    }
+    yb[n] = v;
+    if (cb) cb[n] = (unsigned char)code;
+  }
+  if (peaks) {
+    xpeak = air_wave_max(xpeak);
+    ypeak = air_wave_max(ypeak);
+    if ((t & 63) == 0) {
+      atomic_max_pos(peaks + 2 * b, xpeak);
+      atomic_max_pos(peaks + 2 * b + 1, ypeak);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void g711_clear_peaks_kernel(unsigned* __restrict__ peaks, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) peaks[i] = 0u;
+}
+
+template <typename T>
+int g711_launch(const T* x, int B, int Lcap, const int* lengths, const float* fir, int ntaps, const int* law_idx, int resample,
+                int normalize, float* y, uint8_t* codes, void* ws, hipStream_t st) {
+  unsigned* peaks = normalize ? reinterpret_cast<unsigned*>(ws) : nullptr;
+  if (peaks) {
+    // a kernel, not hipMemsetAsync: this call is meant to be captured, and the memset node of these few bytes was seen to
+    // write a non-zero pattern from the second replay of the graph on (tests/test_codec_gpu.py replays three times)
+    hipLaunchKernelGGL(g711_clear_peaks_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, st, peaks, 2 * B);
+    AIR_CHECK_LAUNCH();
+  }
+  const dim3 grid((Lcap + GC_T - 1) / GC_T, B);
+  if (resample)
+    hipLaunchKernelGGL(g711_resample_kernel<T>, grid, dim3(GC_NT), 0, st, x, Lcap, lengths, fir, ntaps, law_idx, y, codes, peaks);
+  else
+    hipLaunchKernelGGL(g711_code_kernel<T>, grid, dim3(GC_NT), 0, st, x, Lcap, lengths, law_idx, y, codes, peaks);
+  AIR_CHECK_LAUNCH();
+  if (normalize) {
+    hipLaunchKernelGGL(fir_rescale_kernel, dim3(16, B), dim3(256), 0, st, y, Lcap, lengths, law_idx, peaks);
+    AIR_CHECK_LAUNCH();
+  }
+  return AIR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -380,6 +612,22 @@ int air_ir_convolve_ragged(const float* x, const int16_t* x16, int B, int Lcap, 
   if (x16)
     return ir_launch(reinterpret_cast<const short*>(x16), B, Lcap, lengths_dev, irs, n_ir, H, ir_idx, normalize, y, ws, ws_bytes, st);
   return ir_launch(x, B, Lcap, lengths_dev, irs, n_ir, H, ir_idx, normalize, y, ws, ws_bytes, st);
+}
+
+size_t air_g711_ws_bytes(int B) { return air_ir_convolve_ws_bytes(B); }  // the same two peaks per row
+
+int air_g711_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev_or_null, const float* fir,
+                    int ntaps, const int* law_idx, int resample, int normalize, float* y, uint8_t* codes_or_null, void* ws,
+                    size_t ws_bytes, air_stream_t stream) {
+  if ((x != nullptr) == (x16 != nullptr) || !y || B <= 0 || Lcap <= 0 || ntaps < 1 || ntaps > GC_MAXTAPS || !(ntaps & 1) ||
+      (resample && !fir) || (x && x == y))
+    return AIR_EINVAL;
+  if (normalize && (!ws || ws_bytes < air_g711_ws_bytes(B))) return AIR_EWORKSPACE;
+  hipStream_t st = air_stream(stream);
+  if (x16)
+    return g711_launch(reinterpret_cast<const short*>(x16), B, Lcap, lengths_dev_or_null, fir, ntaps, law_idx, resample,
+                       normalize, y, codes_or_null, ws, st);
+  return g711_launch(x, B, Lcap, lengths_dev_or_null, fir, ntaps, law_idx, resample, normalize, y, codes_or_null, ws, st);
 }
 
 }  // extern "C"

@@ -311,6 +311,39 @@ int air_ir_convolve_ragged(const float* x, const int16_t* x16, int B, int Lcap, 
                            const float* irs, int n_ir, int H, const int* ir_idx, int normalize,
                            float* y, void* ws, size_t ws_bytes, air_stream_t stream);
 
+/* G.711 transmission codec ahead of the IR convolution - the first half of channel_simulation/simulated_device_channel.py:
+ * 47-54 (codec, then device), for the two sample-parallel entries of the reference's codec list, G.711 mu-law and A-law
+ * (the adaptive-predictor and whole-file codecs of that list are not covered).  Rows as in air_ir_convolve_ragged:
+ * exactly one of x (fp32) / x16 (16-bit PCM, s / 32768) is non-NULL, row b = x + b * Lcap holds L_b = clamp(lengths[b],
+ * 1, Lcap) samples; a NULL lengths pointer means L_b = Lcap for every row (the dense batch).  law_idx[b] < 0 copies
+ * x[b, :L_b] (converted, for x16); 0 is mu-law; 1 - and anything above, the index being caller data - A-law; a NULL
+ * law_idx is mu-law for every row.  fir is a DEVICE array of ntaps coefficients, ntaps odd in [1, 127], c = (ntaps-1)/2.
+ *   resample != 0, with M_b = ceil(L_b / 2):
+ *     1. u[m] = sum_k fir[k] x[2 m + c - k], m in [0, M_b), x taken as 0 outside [0, L_b); fp32, k ascending;
+ *     2. s = clamp(rint(u * 32768), -32768, 32767) (ties to even), code = G.711 encode(s), d = G.711 decode(code):
+ *        the integer arithmetic of ITU-T G.711 as CPython's audioop states it (mu-law on the top 14 bits of s, A-law on
+ *        the top 13), bit for bit on all 65 536 values of s;
+ *     3. v[m] = d / 32768;
+ *     4. y[n] = 2 sum_k fir[k] vup[n + c - k], n in [0, L_b), vup[2 m] = v[m], 0 at odd positions and outside
+ *        [0, 2 M_b) - evaluated in polyphase form, the stuffed zeros are never multiplied;
+ *   resample == 0: steps 2 and 3 on every input sample at its own rate (M_b = L_b, y[n] = v[n]); fir and ntaps are only
+ *     checked;
+ *   either way, normalize != 0 then rescales each coded row to its input peak over [0, L_b), as air_ir_convolve does.
+ * y is fp32 (B, Lcap), y[b, L_b:] = 0; no input at index >= L_b is read.  codes_or_null, if given, receives the 8-bit
+ * codes of step 2 - (B, (Lcap + 1) / 2) with resample, (B, Lcap) without - with the tail behind M_b and every
+ * pass-through row written as 0.  Nothing depends on Lcap or on the other rows: y[b, :L_b] carries the bits of the call
+ * on that utterance alone.  Lengths and law indices are device data and nothing synchronises with the host, so the call
+ * can be captured in a graph.  ONE launch for the whole batch (grid sized by Lcap; a workgroup stages its 2048 outputs'
+ * input span plus the halo of both filters in LDS, recomputes the 8 kHz samples of the halo, and writes zeros and returns
+ * when it lies wholly behind L_b); with normalize, a small launch that clears the peaks in front of it (a kernel rather
+ * than a memset, so that the captured call replays) and the rescale launch behind it.  Both or neither of x / x16, x == y, a NULL y, a
+ * non-positive size, an even ntaps or one outside [1, 127], resample with a NULL fir: AIR_EINVAL, ahead of any HIP call;
+ * normalize with a workspace below air_g711_ws_bytes(B): AIR_EWORKSPACE. */
+size_t air_g711_ws_bytes(int B);
+int air_g711_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev_or_null,
+                    const float* fir, int ntaps, const int* law_idx, int resample, int normalize,
+                    float* y, uint8_t* codes_or_null, void* ws, size_t ws_bytes, air_stream_t stream);
+
 /* --------------------------------------------------------------- conv1d --
  * nn.Conv1d (stride 1) as used by ecapa_tdnn.py:39,46,55,111,118,140,143, with the
  * conv -> ReLU -> BN ordering of ecapa_tdnn.py:67-69 supported by bias / ReLU epilogues.

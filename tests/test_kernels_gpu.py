@@ -529,7 +529,9 @@ def test_adam_sgd(ops):
     cg = c.cuda()
     ops.sgd_step(cg, g[:256].reshape(1, 256).cuda(), 5e-4)
     np.testing.assert_allclose(cg.cpu().numpy(), (c - 5e-4 * g[:256].reshape(1, 256)).numpy(), atol=1e-7)
+    c1 = c - 5e-4 * g[:256].reshape(1, 256)
     ops.sgd_step(cg, g[:256].reshape(1, 256).cuda(), 5e-4, grad_scale=0.5)
+    np.testing.assert_allclose(cg.cpu().numpy(), (c1 - 5e-4 * (0.5 * g[:256].reshape(1, 256))).numpy(), atol=1e-7)
 
 
 # Winograd F(2x2,3x3) path (conv_wino.hip): every 3x3 / stride 1 / pad 1 forward without fused

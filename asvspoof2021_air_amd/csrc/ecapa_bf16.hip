@@ -518,7 +518,7 @@ __global__ __launch_bounds__(NT) void h_row_stats_bwd_kernel(const u16* __restri
   float k1 = 0.0f;
   if (dstd != nullptr) {
     const float sd = std_[row];
-    if (sd * sd > clamp_min) k1 = dstd[row] / ((float)(T - 1) * sd);
+    if (sd > sqrtf(clamp_min)) k1 = dstd[row] / ((float)(T - 1) * sd);  // (see row_stats_bwd_kernel, ecapa_ops.hip)
   }
   const uint2* __restrict__ px = row_ld(x + row * Tp);
   uint2* pd = row_st(dx + row * Tp);
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(NT) void h_asp_bwd_kernel(const u16* __restrict__ x
   const size_t b = row / C, c = row - b * C;
   const float mu = out[b * 2 * C + c], sg = out[b * 2 * C + C + c];
   const float dmu = dout[b * 2 * C + c], dsg = dout[b * 2 * C + C + c];
-  const float dq = (sg * sg > 1e-4f) ? dsg / (2.0f * sg) : 0.0f;  // the clamp passes no gradient
+  const float dq = (sg > sqrtf(1e-4f)) ? dsg / (2.0f * sg) : 0.0f;  // the clamp passes no gradient
   const float dm = dmu - 2.0f * mu * dq;
   uint2* __restrict__ pw = row_st(w + row * Tp);
   const uint2* __restrict__ px = row_ld(x + row * Tp);

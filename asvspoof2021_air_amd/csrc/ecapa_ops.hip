@@ -203,7 +203,9 @@ __global__ __launch_bounds__(NT) void row_stats_bwd_kernel(
   float k1 = 0.0f;
   if (dstd != nullptr) {
     const float sd = std_[row];
-    if (sd * sd > clamp_min) k1 = dstd[row] / ((float)(T - 1) * sd);
+    // the forward stores exactly sqrtf(clamp_min) for a clamped row and sqrtf is monotone: sd * sd > clamp_min
+    // would depend on how sqrtf(clamp_min)^2 rounds (true for a clamped row at 1e-3 and 1e-2)
+    if (sd > sqrtf(clamp_min)) k1 = dstd[row] / ((float)(T - 1) * sd);
   }
   // relu_mask: x is a ReLU output (ecapa_tdnn.py:173) and dx the gradient w.r.t. its pre-activation;
   // rowsum[row] = sum_t of the result (its sum over b is the conv bias gradient)
@@ -357,7 +359,7 @@ __global__ __launch_bounds__(NT) void asp_bwd_kernel(const float* __restrict__ x
   const size_t b = row / C, c = row - b * C;
   const float mu = out[b * 2 * C + c], sg = out[b * 2 * C + C + c];
   const float dmu = dout[b * 2 * C + c], dsg = dout[b * 2 * C + C + c];
-  const float dq = (sg * sg > 1e-4f) ? dsg / (2.0f * sg) : 0.0f;  // clamp passes no gradient
+  const float dq = (sg > sqrtf(1e-4f)) ? dsg / (2.0f * sg) : 0.0f;  // clamp passes no gradient
   const float dm = dmu - 2.0f * mu * dq;
   float* __restrict__ pw = w + row * T;
   const float* __restrict__ px = x + row * T;

@@ -138,57 +138,194 @@ def test_res2_se_copy(oh, shape):
     assert torch.equal(back, x)
 
 
-@pytest.mark.parametrize("shape", [(2, 96, 96), (2, 64, 750)])
-def test_row_stats_asp(oh, shape):
-    B, C, T = shape
-    x, xd = res(oh, F.relu(synth_feat(shape, 21)))
-    mean, std = oh.row_stats(x, T)
-    close32(mean, xd.mean(2), "row mean")
-    close32(std, torch.sqrt(xd.var(2).clamp(min=1e-4)), "row std")
-    dmean, dstd = synth_feat((B, C), 22), synth_feat((B, C), 23)
-    dx, dxd = res(oh, synth_feat(shape, 24))
-    xg = xd.clone().requires_grad_(True)
-    (xg.mean(2) * dmean.double()).sum().backward()
-    g1 = xg.grad.clone()
-    xg.grad = None
-    (torch.sqrt(xg.var(2).clamp(min=1e-4)) * dstd.double()).sum().backward()
-    want = (dxd + g1 + xg.grad) * (xd > 0).double()
-    rowsum = torch.empty((B, C), device="cuda")
-    oh.row_stats_bwd(x, T, mean, std, dmean.cuda(), dstd.cuda(), dx, accumulate=True, relu_mask=True, rowsum=rowsum)
-    ulp_ok(val(dx, T), want, "row_stats_bwd", slack=0.56, floor=float(want.abs().max()) * 2e-3)
-    close32(rowsum, val(dx, T).sum(2), "rowsum of the stored values", 1e-5)
+SENT16 = 0x4B3C  # sentinel behind every guarded resident buffer (a bf16 of 1.2e7 no kernel here produces)
+
+
+def guarded_rows(oh, B, C, T, fill=None):
+    """A (B, C, Tp) resident buffer with four more rows of sentinels behind it; returns (view, check)."""
+    Tp = oh.tp(T)
+    raw = torch.full(((B * C + 4) * Tp,), SENT16, dtype=torch.int16, device="cuda")
+    view = raw[:B * C * Tp].view(B, C, Tp)
+    if fill is not None:
+        view.copy_(fill)
+
+    def check(what):
+        assert bool((raw[B * C * Tp:] == SENT16).all()), what + " wrote behind its last row"
+    return view, check
+
+
+def guarded_f32(shape):
+    n = int(np.prod(shape))
+    raw = torch.full((n + 64,), 1.2345678e7, dtype=torch.float32, device="cuda")
+
+    def check(what):
+        assert bool((raw[n:] == 1.2345678e7).all()), what + " wrote behind its buffer"
+    return raw[:n].view(shape), check
+
+
+def _row_stats_asp(oh, xf, lgf, clamp_min=1e-4, dx_in_scale=1.0, want_clamped=None):
+    """Context statistics and attentive pooling on the bf16 values of xf (B, C, T) / logits lgf, against fp64."""
+    B, C, T = xf.shape
+    shape = (B, C, T)
+    c = float(np.float32(clamp_min))
+    x, xd = res(oh, xf)
+    if T >= 2:  # (the deviation needs two frames: air_h_row_stats refuses std at T = 1)
+        mean, std = oh.row_stats(x, T, clamp_min=clamp_min)
+        close32(mean, xd.mean(2), "row mean")
+        close32(std, torch.sqrt(xd.var(2).clamp(min=c)), "row std")
+        if want_clamped is not None:
+            assert (xd.var(2) <= c).tolist() == want_clamped
+            sd = torch.tensor(float(np.sqrt(np.float32(clamp_min))), dtype=torch.float32)
+            assert bool((std.cpu()[torch.tensor(want_clamped)] == sd).all()), "a clamped row's std is not sqrt(float32(clamp_min))"
+        dmean, dstd = synth_feat((B, C), 22), synth_feat((B, C), 23)
+        dx0, dxd = res(oh, dx_in_scale * synth_feat(shape, 24))
+        dx, dx_check = guarded_rows(oh, B, C, T, fill=dx0)
+        xg = xd.clone().requires_grad_(True)
+        (xg.mean(2) * dmean.double()).sum().backward()
+        g1 = xg.grad.clone()
+        xg.grad = None
+        (torch.sqrt(xg.var(2).clamp(min=c)) * dstd.double()).sum().backward()
+        want = (dxd + g1 + xg.grad) * (xd > 0).double()
+        rowsum, rs_check = guarded_f32((B, C))
+        oh.row_stats_bwd(x, T, mean, std, dmean.cuda(), dstd.cuda(), dx, accumulate=True, clamp_min=clamp_min, relu_mask=True,
+                         rowsum=rowsum)
+        dx_check("row_stats_bwd")
+        rs_check("row_stats_bwd rowsum")
+        ulp_ok(val(dx, T), want, "row_stats_bwd", slack=0.56, floor=float(want.abs().max()) * 2e-3)
+        close32(rowsum, val(dx, T).sum(2), "rowsum of the stored values", 1e-5)
+    else:
+        mean, _ = oh.row_stats(x, T, want_std=False)
+        close32(mean, xd.mean(2), "row mean")
     # attentive statistics pooling
-    lg, lgd = res(oh, 2.0 * synth_feat(shape, 25))
-    w = lg.clone()
+    lg, lgd = res(oh, lgf)
+    w, w_check = guarded_rows(oh, B, C, T, fill=lg)
     out = oh.asp_fwd(x, w, T)
+    w_check("asp_fwd")
+    assert bool(torch.isfinite(out).all())
     wd = torch.softmax(lgd, 2)
     ulp_ok(val(w, T), wd, "asp softmax", slack=0.56)
     ws = val(w, T)  # the stored weights define the pooled statistics
     mu = (xd * ws).sum(2)
-    sg = torch.sqrt(((xd ** 2) * ws).sum(2) - mu ** 2).clamp(min=1e-2)
-    sg = torch.sqrt((((xd ** 2) * ws).sum(2) - mu ** 2).clamp(min=1e-4))
+    q = ((xd ** 2) * ws).sum(2) - mu ** 2
+    sg = torch.sqrt(q.clamp(min=1e-4))
     close32(out[:, :C], mu, "asp mu")
     close32(out[:, C:], sg, "asp sg", 1e-4)
     # backward: stored w as a leaf
     dout = synth_feat((B, 2 * C), 26)
-    xl = xd.clone().requires_grad_(True)
-    al = lgd.clone().requires_grad_(True)
-    wl = torch.softmax(al, 2)
     # the kernel differentiates through softmax at the STORED weights: evaluate the analytic formula there
     dm_, ds_ = dout.double()[:, :C], dout.double()[:, C:]
-    dq = torch.where(sg * sg > 1e-4, ds_ / (2 * sg), torch.zeros_like(sg))
+    # (clamped where sg^2 == the clamp; decided on q, not on sqrt(1e-4)^2, which need not round back to 1e-4)
+    dq = torch.where(q > 1e-4, ds_ / (2 * sg), torch.zeros_like(sg))
     dmm = dm_ - 2 * mu * dq
     dwv = dmm[:, :, None] * xd + dq[:, :, None] * xd ** 2
     want_dx = dmm[:, :, None] * ws + 2 * dq[:, :, None] * xd * ws
     dot = (ws * dwv).sum(2, keepdim=True)
     want_da = ws * (dwv - dot)
-    dxo = oh.rows(B, C, T, "cuda")
-    rs = torch.empty((B, C), device="cuda")
+    dxo, dxo_check = guarded_rows(oh, B, C, T)
+    rs, rs_check = guarded_f32((B, C))
     oh.asp_bwd(x, w, T, out, dout.cuda(), dxo, rowsum=rs)
+    dxo_check("asp_bwd dx")
+    w_check("asp_bwd d logits")
+    rs_check("asp_bwd rowsum")
     ulp_ok(val(dxo, T), want_dx, "asp_bwd dx", slack=0.6, floor=float(want_dx.abs().max()) * 2e-3)
     ulp_ok(val(w, T), want_da, "asp_bwd dlogits", slack=0.6, floor=float(want_da.abs().max()) * 2e-3)
     # (analytically zero - softmax over T is shift-invariant: compare on the scale of the summed magnitudes)
     assert float((rs.cpu().double() - val(w, T).sum(2)).abs().max()) <= 1e-5 * float(val(w, T).abs().sum(2).max())
+    return out
+
+
+def _se(oh, shape, z=None):
+    """SE gate + residual and its backward, with the output and the incoming gradient as channel slices."""
+    B, C, T = shape
+    x, xd = res(oh, synth_feat(shape, 11))
+    add, addd = res(oh, synth_feat(shape, 12))
+    z = synth_feat((B, C), 15) if z is None else z
+    wide, wide_check = guarded_rows(oh, B, C + 2, T)
+    wide.zero_()
+    oh.se_scale_fwd(x, z.cuda(), add, T, wide[:, 1:C + 1])
+    wide_check("se_scale_fwd")
+    g = torch.sigmoid(z.double())[:, :, None]
+    ulp_ok(val(wide[:, 1:C + 1].contiguous(), T), xd * g + addd, "se_scale_fwd")
+    assert int(wide[:, :1].abs().max()) == 0 and int(wide[:, C + 1:].abs().max()) == 0
+    dwide = oh.rows(B, C + 3, T, "cuda", zero=True)
+    dout, doutd = res(oh, synth_feat(shape, 16))
+    dwide[:, 2:C + 2] = dout
+    dx, dz = oh.se_scale_bwd(x, z.cuda(), dwide[:, 2:C + 2], T)
+    assert bool(torch.isfinite(dz).all())
+    ulp_ok(val(dx, T), doutd * g, "se_scale_bwd dx")
+    close32(dz, (doutd * xd).sum(2) * (g * (1 - g))[:, :, 0], "se_scale_bwd dz", 1e-4)
+    return val(dx, T), doutd, dz
+
+
+@pytest.mark.parametrize("shape", [(2, 96, 96), (2, 64, 750)])
+def test_row_stats_asp(oh, shape):
+    _row_stats_asp(oh, F.relu(synth_feat(shape, 21)), 2.0 * synth_feat(shape, 25))
+
+
+@pytest.mark.parametrize("BC", [(1, 1), (1, 7), (3, 5), (2, 6)])
+def test_row_kernels_ragged_last_workgroup(oh, BC):
+    """B * C = 1, 7, 15 leave rows of the last workgroup (4 waves, one row each) for the guard to reject."""
+    shape = BC + (96,)
+    _row_stats_asp(oh, F.relu(synth_feat(shape, 21)), 2.0 * synth_feat(shape, 25))
+    _se(oh, shape)
+
+
+# Tp = 256 ceil(T / 256): Tp - T = 0, 1, 255 (the largest), a one-frame row, and all HMAXV = 8 vectors per lane live
+@pytest.mark.parametrize("T", [256, 255, 257, 1, 1800])
+def test_row_kernels_length_edges(oh, T):
+    assert oh.tp(T) - T == {256: 0, 255: 1, 257: 255, 1: 255, 1800: 248}[T] and (T != 1800 or oh.tp(T) == oh.max_tp())
+    shape = (1, 3, T)
+    _row_stats_asp(oh, F.relu(synth_feat(shape, 21)) + 0.125, 2.0 * synth_feat(shape, 25))
+    _se(oh, shape)
+
+
+def test_row_kernels_refuse_rows_longer_than_the_register_cache(oh):
+    """Tp = 2304 > 256 * HMAXV: every row kernel answers with the error code instead of launching."""
+    from asvspoof2021_air_amd import _hip
+    B, C, T = 1, 3, 2049
+    x = oh.rows(B, C, T, "cuda", zero=True)
+    assert x.shape[2] == 2304 > oh.max_tp()
+    f2 = torch.zeros((B, C), device="cuda")
+    out = torch.zeros((B, 2 * C), device="cuda")
+    calls = [lambda: oh.row_stats(x, T), lambda: oh.row_stats_bwd(x, T, f2, f2, f2, f2, x.clone()),
+             lambda: oh.asp_fwd(x, x.clone(), T), lambda: oh.asp_bwd(x, x.clone(), T, out, out, x.clone()),
+             lambda: oh.se_scale_fwd(x, f2, x, T, x.clone()), lambda: oh.se_scale_bwd(x, f2, x, T)]
+    for call in calls:
+        with pytest.raises(_hip.AirError, match="AIR_EINVAL"):
+            call()
+
+
+@pytest.mark.parametrize("clamp_min", [1e-4, 1e-3, 1e-2])
+def test_row_stats_clamp_branches(oh, clamp_min):
+    """Rows: all zero (a dead channel behind the ReLU) | constant 5 | std 0.5 sqrt(c) | std 2 sqrt(c) | noise.  The
+    first three are clamped: std == sqrt(float32(c)) bit for bit and no dstd term in dx (autograd's clamp(min=) passes
+    none).  The 0.5 sqrt(c) row is the one whose x - mean is not zero: with the predicate sd * sd > clamp_min it got the
+    dstd term at 1e-3 and 1e-2.  The incoming dx is zero so that the term is not lost below a bf16 ulp of it."""
+    import ecapa_rows_oracle as eo
+    xf = torch.from_numpy(eo.clamp_rows(clamp_min))
+    _row_stats_asp(oh, xf, 2.0 * synth_feat(tuple(xf.shape), 25), clamp_min=clamp_min, dx_in_scale=0.0,
+                   want_clamped=[[True, True, True, False, False]])
+
+
+def test_asp_softmax_range(oh):
+    """Logits in [-60, -40] | one logit 100 above the rest | all equal | constant x | zero x: finite and within the
+    bounds.  The one-hot row (its stored weight is exactly 1) and the zero row cancel sg^2 to the clamp.  The constant-x
+    row does not here: the STORED bf16 weights sum to S = 1 +- a few 1e-3, so sg^2 = S (1 - S) ~ 1.6e-4 - the value the
+    fp64 reference at the stored weights has too."""
+    import ecapa_rows_oracle as eo
+    x, a = eo.softmax_range_rows()
+    out = _row_stats_asp(oh, torch.from_numpy(x), torch.from_numpy(a))
+    sg = out[0, 5:].cpu()
+    assert bool((sg[[1, 4]] == torch.tensor(np.float32(0.01))).all())
+    # every exp() underflows unless the row maximum is subtracted (a maximum that starts at 0 would leave 0 / 0)
+    _row_stats_asp(oh, F.relu(synth_feat((1, 3, 83), 21)), torch.from_numpy(eo.deep_negative_logits((1, 3, 83))))
+
+
+def test_se_gate_range(oh):
+    z = torch.tensor([[0.0, 20.0, -20.0, 88.0, -88.0, 100.0, -100.0, 1e4, -1e4]])
+    dx, doutd, dz = _se(oh, (1, 9, 61), z=z)
+    assert torch.equal(dx[0, [1, 3, 5, 7]], doutd[0, [1, 3, 5, 7]]), "g must saturate to exactly 1"
+    assert bool((dx[0, [6, 8]] == 0).all()) and bool((dz[0, [1, 3, 5, 7, 6, 8]] == 0).all())
 
 
 POINTWISE = [(2, 512, 512, 750), (3, 1536, 1536, 96), (2, 1536, 128, 401), (2, 128, 1536, 401), (4, 512, 512, 96)]

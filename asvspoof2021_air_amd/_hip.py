@@ -39,6 +39,23 @@ class AirConv1d(ctypes.Structure):
         ("x_bstride", ctypes.c_size_t), ("y_bstride", ctypes.c_size_t)]
 
 
+ADV_MAX_HEADS = 4
+
+
+class AirAdvHead(ctypes.Structure):
+    _fields_ = [("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("targets", ctypes.c_void_p), ("keep", ctypes.c_void_p), ("counter", ctypes.c_void_p),
+                ("seed", ctypes.c_uint64), ("grads", ctypes.c_void_p), ("loss", ctypes.c_void_p),
+                ("correct", ctypes.c_void_p), ("run_correct", ctypes.c_void_p), ("C", ctypes.c_int),
+                ("p", ctypes.c_float)]
+
+
+class AirAdvHeads(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("D", ctypes.c_int), ("nheads", ctypes.c_int), ("want_dx", ctypes.c_int),
+                ("lambda_", ctypes.c_float), ("feats", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+                ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t), ("head", AirAdvHead * ADV_MAX_HEADS)]
+
+
 def lib_path():
     return _LIB_PATH
 
@@ -75,7 +92,7 @@ def lib():
         for name in ("air_conv2d_ws_bytes", "air_bn_ws_bytes", "air_conv1d_ws_bytes", "air_conv1d_bf16_ws_bytes",
                      "air_channel_sum_ws_bytes", "air_ir_convolve_ws_bytes", "air_ir_convolve_ws_bytes_ex", "air_g711_ws_bytes", "air_conv2d_prepack_bytes",
                      "air_conv1d_tap_pack_elems", "air_h_bn_ws_bytes", "air_h_conv1d_ws_bytes", "air_conv2d_fwd_stats_bytes", "air_conv2d_dgrad_bn_sums_bytes", "air_conv2d_dgrad_s2_pair_prepack_bytes", "air_h_conv1d_tap_stats_bytes", "air_h_conv1d_tap_bwd_sums_bytes", "air_h_conv1d_pointwise_stats_bytes",
-                     "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes"):
+                     "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes", "air_adv_heads_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_size_t
     return _lib

@@ -618,6 +618,82 @@ def dropout_mask_ctr(shape, p, seed, counter, device):
     return keep
 
 
+class AdvHead:
+    """One channel-classifier head as ``adv_heads`` takes it: ``flat`` = [w1 (H, D) | b1 (H) | w2 (C, H) | b2 (C)] in one
+    fp32 block, ``grad`` the gradient block of the same layout, ``p`` the dropout probability in force (0: eval),
+    ``seed`` / ``counter`` (1-element int64 GPU tensor) the in-kernel draw's Philox key and device-side offset."""
+
+    def __init__(self, flat, grad, nclasses, p=0.0, seed=0, counter=None):
+        self.flat, self.grad, self.nclasses, self.p, self.seed, self.counter = flat, grad, int(nclasses), float(p), int(seed), counter
+
+
+def adv_head_numel(D, C):
+    H = D // 2
+    return H * D + H + C * H + C
+
+
+def adv_heads(feats, heads, targets, lambda_, want_dx, keeps=None, run_correct=None):
+    """Every classifier head of one phase of the --ADV_AUG step in one fused call (air_adv_heads): ``feats`` (B, D) fp32,
+    ``heads`` 1 - 4 ``AdvHead``-like objects, ``targets`` one int64 (B,) tensor per head, ``keeps`` optional explicit
+    scaled keep masks (B, D // 2) per head (None entries: the head's own draw, or none), ``run_correct`` optional int64
+    (n,) running totals.  Returns (losses (n,), correct (n,) int32, dx (B, D) or None); the gradients are written
+    into the heads' ``grad`` blocks."""
+    n = len(heads)
+    if not 1 <= n <= _hip.ADV_MAX_HEADS or len(targets) != n or (keeps is not None and len(keeps) != n):
+        raise ValueError("adv_heads takes 1 - %d heads with one target tensor (and keep mask) each" % _hip.ADV_MAX_HEADS)
+    if feats.dim() != 2:
+        raise ValueError("expected (B, D) features")
+    B, D = feats.shape
+    H = D // 2
+    dev = feats.device
+    losses = torch.empty(n, device=dev, dtype=torch.float32)
+    correct = torch.empty(n, device=dev, dtype=torch.int32)
+    dx = torch.empty(B, D, device=dev, dtype=torch.float32) if want_dx else None
+    if run_correct is not None and (run_correct.dtype != torch.int64 or run_correct.numel() != n):
+        raise _hip.AirError("adv_heads: run_correct must be an int64 GPU tensor with one entry per head")
+    d = _hip.AirAdvHeads()
+    d.B, d.D, d.nheads, d.want_dx, d.lambda_ = B, D, n, int(bool(want_dx)), float(lambda_)
+    d.feats = dptr(feats).value
+    d.dx = dptr(dx, allow_none=True).value
+    counts = (ctypes.c_int * n)(*[int(h.nclasses) for h in heads])
+    nbytes = _hip.lib().air_adv_heads_ws_bytes(ci(B), ci(D), ci(n), counts, ci(d.want_dx))
+    if nbytes == 0:
+        raise _hip.AirError("adv_heads: unsupported shape B=%d D=%d classes=%s" % (B, D, list(counts)))
+    ws = workspace(nbytes, dev)
+    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
+    hold = []
+    for k, h in enumerate(heads):
+        C = int(h.nclasses)
+        if h.flat.numel() != adv_head_numel(D, C) or h.grad.numel() != h.flat.numel():
+            raise _hip.AirError("adv_heads: head %d's blocks do not hold a (%d -> %d -> %d) classifier" % (k, D, H, C))
+        tgt = targets[k]
+        if tgt.numel() != B:
+            raise ValueError("adv_heads: head %d needs %d targets, got %d" % (k, B, tgt.numel()))
+        base, gbase = dptr(h.flat).value, dptr(h.grad).value
+        e = d.head[k]
+        e.w1, e.b1, e.w2, e.b2 = base, base + 4 * H * D, base + 4 * (H * D + H), base + 4 * (H * D + H + C * H)
+        e.targets = dptr(tgt, torch.int64).value
+        keep = keeps[k] if keeps is not None else None
+        if keep is not None:
+            if tuple(keep.shape) != (B, H):
+                raise ValueError("adv_heads: keep mask of head %d must be (%d, %d)" % (k, B, H))
+            e.keep = dptr(keep).value
+        ctr = getattr(h, "counter", None)
+        if ctr is not None:
+            if ctr.dtype != torch.int64 or not ctr.is_cuda or ctr.numel() != 1:
+                raise _hip.AirError("adv_heads: counter must be a 1-element int64 GPU tensor")
+            e.counter = ctr.data_ptr()
+        e.seed, e.C, e.p = int(h.seed) & 0xFFFFFFFFFFFFFFFF, C, float(h.p)
+        e.grads = gbase
+        e.loss = losses.data_ptr() + 4 * k
+        e.correct = correct.data_ptr() + 4 * k
+        if run_correct is not None:
+            e.run_correct = dptr(run_correct, torch.int64).value + 8 * k
+        hold.append((tgt, keep, ctr))
+    _hip.check(_hip.lib().air_adv_heads(ctypes.byref(d), stream()), "air_adv_heads")
+    return losses, correct, dx
+
+
 # ------------------------------------------------------------------ Res2Net (res2net.py)
 def sptr(t):
     """(pointer, batch stride) of a (B, C, H, W) fp32 GPU tensor or channel-slice view whose (C, H, W) block is

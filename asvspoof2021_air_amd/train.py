@@ -420,6 +420,7 @@ class Trainer:
                 g["start"].zero_()
             else:
                 g["start"].copy_(torch.as_tensor(start), non_blocking=True)
+        self._refresh_tail(g)
         # graph k's replay, then (world > 1, segments) the all-reduce of the arena slice it completed - launched on the
         # communication stream behind an event, so that the next replay is enqueued right away
         bucketer = None
@@ -446,7 +447,20 @@ class Trainer:
                 self.model._bucketer = None
             scale = 1.0 / self.world
         self._optimise(scale)
+        self._replay_tail(g, scale)
         return g["loss"].detach().clone(), (g["neg"].clone() if g["neg"] is not None else None)
+
+    # A subclass whose step goes on behind the optimisers (adversarial.AdversarialTrainer: the classifiers' phase)
+    # captures that part as a graph of the same pool (``captured(fn) -> (graph, fn())``), refreshes its static inputs
+    # before the replays and replays it behind ``_optimise``.
+    def _capture_tail(self, captured):
+        return None
+
+    def _refresh_tail(self, g):
+        pass
+
+    def _replay_tail(self, g, scale):
+        pass
 
     def _ragged_lengths(self, lengths, pcm):
         """``lengths`` as the int32 (B,) device tensor a replay copies into the capture's buffer; host values are checked
@@ -564,6 +578,22 @@ class Trainer:
                     raise
                 state["g"].capture_end()
                 graphs.append((state["g"], None))  # the rest of the arena goes with the final all-reduce
+                self.model._segment_cut = None
+
+                def captured(fn):
+                    graph = torch.cuda.CUDAGraph()
+                    graph.capture_begin(pool=pool, capture_error_mode=mode)
+                    try:
+                        out = fn()
+                    except BaseException:
+                        try:
+                            graph.capture_end()
+                        except Exception:  # noqa: BLE001
+                            pass
+                        raise
+                    graph.capture_end()
+                    return graph, out
+                tail = self._capture_tail(captured)
         finally:
             self.model._segment_cut = None
         torch.cuda.current_stream().wait_stream(cap)
@@ -574,7 +604,7 @@ class Trainer:
         # p.grad now ARE the tensors the captured kernels write (no zero_grad between replays - every gradient is
         # overwritten, none accumulated); kept in "grads" so _graphed_step can restore them after eager interludes
         self._graph = dict(key=key, graphs=graphs, segments=graphs if self.graph_segments else None, pool=pool, pcm=s_pcm,
-                           labels=s_labels, lengths=s_len, start=s_start, loss=loss, neg=neg, grads=grads,
+                           labels=s_labels, lengths=s_len, start=s_start, loss=loss, neg=neg, grads=grads, tail=tail,
                            ws_gen=ops.workspace_generation())
         return self._graph
 

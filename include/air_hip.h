@@ -807,6 +807,53 @@ int air_mul(const float* a, const float* b, size_t n, float* y, air_stream_t str
  * air_dropout_mask (adv_head.hip).  counter: 8-byte aligned. */
 int air_dropout_mask_ctr(float* keep, size_t n, float p, uint64_t seed, uint64_t* counter, air_stream_t stream);
 
+/* ------------------------------------------- fused adversarial heads ------
+ * All channel-classifier heads of one phase of the --ADV_AUG step in one call (csrc/adv_head.hip): per head k
+ * GRL -> Linear(D, D/2) -> Dropout(p) -> ReLU -> Linear(D/2, C_k) -> ReLU (model.py:976-1023), the mean cross-entropy
+ * and the accuracy count of main_train.py:381-387 / :426-432, and the backward of :394-402 / :441-453:
+ *   h = relu(keep * (w1 x + b1)),  o = relu(w2 h + b2),  loss_k = mean_b CE(o_b, targets_b),
+ *   correct_k = #(first argmax == target)   (a row of zeros predicts class 0, as air_softmax_ce_fwd),
+ *   grads = [dw1 (H, D) | db1 (H) | dw2 (C, H) | db2 (C)] of loss_k, written (not accumulated), H = D / 2,
+ *   dx (want_dx) = t_0 + t_1 + ... in head order, t_k = -lambda * d loss_k / d feats (lambda multiplied in last).
+ * One workgroup per head; with several heads and want_dx a second launch adds the heads' terms.  Fixed summation
+ * order, no floating-point atomics: the same inputs give the same bits.  Softmax and CE are the arithmetic of
+ * air_softmax_ce_fwd / _bwd.
+ * Dropout: `keep` (B, H), already scaled, is used as given; else with p > 0 and a `counter` (8-byte aligned device
+ * uint64, one per head, not shared between heads) the mask is air_dropout_mask_ctr's draw - Philox(seed, *counter + quad)
+ * over the flattened (B, H) mask - and the call advances the counter by (B * H + 3) / 4; else there is no mask (eval).
+ * run_correct (optional, device int64): correct_k is added to it.
+ * ws: air_adv_heads_ws_bytes(B, D, nheads, C, want_dx) bytes of device scratch (0 = unsupported arguments).
+ * Supported: 1 <= B <= 4096; D even, 2 <= D <= 1024; 1 <= C_k <= 256; 1 <= nheads <= 4; 0 <= p < 1.  Anything else, a
+ * NULL pointer, a short workspace or a misaligned / shared counter: AIR_EINVAL, ahead of any HIP call. */
+#define AIR_ADV_MAX_HEADS 4
+typedef struct AirAdvHead {
+  const float* w1;             /* (H, D) */
+  const float* b1;             /* (H) */
+  const float* w2;             /* (C, H) */
+  const float* b2;             /* (C) */
+  const long long* targets;    /* (B) int64 */
+  const float* keep;           /* (B, H) explicit scaled keep mask, or NULL */
+  uint64_t* counter;           /* device Philox offset, or NULL */
+  uint64_t seed;
+  float* grads;                /* H*D + H + C*H + C floats */
+  float* loss;                 /* device scalar */
+  int* correct;                /* device scalar */
+  long long* run_correct;      /* device scalar, or NULL */
+  int C;
+  float p;
+} AirAdvHead;
+typedef struct AirAdvHeads {
+  int B, D, nheads, want_dx;
+  float lambda;
+  const float* feats;          /* (B, D) */
+  float* dx;                   /* (B, D) when want_dx */
+  void* ws;
+  size_t ws_bytes;
+  AirAdvHead head[AIR_ADV_MAX_HEADS];
+} AirAdvHeads;
+size_t air_adv_heads_ws_bytes(int B, int D, int nheads, const int* C, int want_dx);
+int air_adv_heads(const AirAdvHeads* d, air_stream_t stream);
+
 /* -------------------------------------------------------------- Res2Net ---
  * model.Res2Net(SEBottle2neck, [3, 4, 6, 3], baseWidth=26, scale=4) (model.py:256-509, main_train.py:169-170).
  * Its BatchNorms run on the BatchNorm kernels, the SE squeeze and the global average pool on air_row_stats, the SE

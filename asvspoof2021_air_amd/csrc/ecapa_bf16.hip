@@ -255,9 +255,13 @@ __global__ __launch_bounds__(NT) void h_res2_kernel(const u16* __restrict__ x, s
 }
 
 // ---- SE gate + block residual (ecapa_tdnn.py:27-29, :93): out = bf16(x * sigmoid(z[b][c]) + res)
+// SUM (summed=True, ecapa_tdnn.py:163-166): the running sum of the block inputs leaves the same pass,
+// sum = bf16(out + res) on the STORED out (autocast's bf16 + bf16 add) - no second read of either tensor
+template <bool SUM>
 __global__ __launch_bounds__(NT) void h_se_fwd_kernel(const u16* __restrict__ x, size_t xbs, const float* __restrict__ z,
                                                       const u16* __restrict__ res, size_t rbs, int C, int T, int Tp,
-                                                      u16* __restrict__ out, size_t obs, size_t rows) {
+                                                      u16* __restrict__ out, size_t obs, u16* __restrict__ sum, size_t sbs,
+                                                      size_t rows) {
   const size_t row = (size_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
@@ -266,12 +270,42 @@ __global__ __launch_bounds__(NT) void h_se_fwd_kernel(const u16* __restrict__ x,
   const uint2* __restrict__ px = row_ld(x + b * xbs + c * Tp);
   const uint2* __restrict__ pr = row_ld(res + b * rbs + c * Tp);
   uint2* __restrict__ po = row_st(out + b * obs + c * Tp);
+  uint2* __restrict__ ps = SUM ? row_st(sum + b * sbs + c * Tp) : nullptr;
   for (int i = lane; i < Tp / 4; i += 64) {
     float v[4], r[4];
     unpack4(px[i], v);
     unpack4(pr[i], r);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], g, r[e]);
+    const uint2 o = pack4_masked(v, 4 * i, T);
+    po[i] = o;
+    if (SUM) {
+      float w[4];
+      unpack4(o, w);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w[e] += r[e];
+      ps[i] = pack4_masked(w, 4 * i, T);
+    }
+  }
+}
+
+// ---- out = bf16(a + b) on resident rows / channel slices (summed=True backward: d x_k = its slice of the concat
+// gradient + d s_k).  out may alias a or b ELEMENT FOR ELEMENT (each lane reads its 8 bytes before it writes them)
+__global__ __launch_bounds__(NT) void h_add_kernel(const u16* a, size_t abs_, const u16* b, size_t bbs, int C, int T, int Tp,
+                                                   u16* out, size_t obs, size_t rows) {
+  const size_t row = (size_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const size_t n = row / C, c = row - n * C;
+  const uint2* pa = row_ld(a + n * abs_ + c * Tp);
+  const uint2* pb = row_ld(b + n * bbs + c * Tp);
+  uint2* po = row_st(out + n * obs + c * Tp);
+  for (int i = lane; i < Tp / 4; i += 64) {
+    float v[4], w[4];
+    unpack4(pa[i], v);
+    unpack4(pb[i], w);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += w[e];
     po[i] = pack4_masked(v, 4 * i, T);
   }
 }
@@ -543,6 +577,36 @@ __global__ __launch_bounds__(NT) void h_row_stats_bwd_kernel(const u16* __restri
   }
 }
 
+// context=False (ecapa_tdnn.py:179-180): no statistics rows feed attention.0, so d(x4) only takes layer4's ReLU mask
+// (:173) and the per-row sums of the bias gradient.  dx = bf16(0 + dx) where x > 0, else 0 - the value
+// h_row_stats_bwd_kernel stores with zero dmean / dstd (0 + dx: a stored -0 leaves as +0 there as well) - and
+// rowsum[row] = sum_t of the STORED values in that kernel's order; reads no statistics.  In place on dx.
+__global__ __launch_bounds__(NT) void h_relu_mask_rowsum_kernel(const u16* __restrict__ x, size_t xbs, int C, int T, int Tp,
+                                                                u16* dx, size_t dbs, float* __restrict__ rowsum,
+                                                                size_t rows) {
+  const size_t row = (size_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const size_t b = row / C, c = row - b * C;
+  const uint2* __restrict__ px = row_ld(x + b * xbs + c * Tp);
+  uint2* pd = row_st(dx + b * dbs + c * Tp);
+  float s = 0.0f;
+  for (int i = lane; i < Tp / 4; i += 64) {
+    float xv[4], d[4];
+    unpack4(px[i], xv);
+    unpack4(pd[i], d);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = xv[e] > 0.0f ? 0.0f + d[e] : 0.0f;
+    const uint2 o = pack4_masked(d, 4 * i, T);
+    pd[i] = o;
+    s += (lo_f(o.x) + hi_f(o.x)) + (lo_f(o.y) + hi_f(o.y));
+  }
+  if (rowsum != nullptr) {
+    s = air_wave_sum(s);
+    if (lane == 0) rowsum[row] = s;
+  }
+}
+
 // ---- attentive statistics pooling (ecapa_tdnn.py:143-185).  a (logits, bf16) is overwritten with
 // w = bf16(softmax_T(a)); mu = sum x w, sg = sqrt(clamp(sum x^2 w - mu^2, 1e-4)) with the STORED w.
 __global__ __launch_bounds__(NT) void h_asp_fwd_kernel(const u16* __restrict__ x, u16* __restrict__ a, int C, int T, int Tp,
@@ -796,8 +860,50 @@ int air_h_se_scale_fwd(const unsigned short* x, size_t x_bs, const float* z, con
                        int B, int C, int T, int Tp, unsigned short* out, size_t out_bs, air_stream_t stream) {
   if (!x || !z || !res || !out || !h_shape_ok(B, C, T, Tp)) return AIR_EINVAL;
   const size_t rows = (size_t)B * C;
-  hipLaunchKernelGGL(h_se_fwd_kernel, dim3(h_row_grid(rows)), dim3(NT), 0, air_stream(stream), x, bs_or(x_bs, C, Tp), z,
-                     res, bs_or(res_bs, C, Tp), C, T, Tp, out, bs_or(out_bs, C, Tp), rows);
+  hipLaunchKernelGGL(h_se_fwd_kernel<false>, dim3(h_row_grid(rows)), dim3(NT), 0, air_stream(stream), x, bs_or(x_bs, C, Tp),
+                     z, res, bs_or(res_bs, C, Tp), C, T, Tp, out, bs_or(out_bs, C, Tp), (u16*)nullptr, (size_t)0, rows);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_h_se_scale_fwd_sum(const unsigned short* x, size_t x_bs, const float* z, const unsigned short* res, size_t res_bs,
+                           int B, int C, int T, int Tp, unsigned short* out, size_t out_bs, unsigned short* sum,
+                           size_t sum_bs, air_stream_t stream) {
+  if (!x || !z || !res || !out || !sum || sum == out || sum == res || sum == x || !h_shape_ok(B, C, T, Tp)) return AIR_EINVAL;
+  const size_t rows = (size_t)B * C;
+  hipLaunchKernelGGL(h_se_fwd_kernel<true>, dim3(h_row_grid(rows)), dim3(NT), 0, air_stream(stream), x, bs_or(x_bs, C, Tp),
+                     z, res, bs_or(res_bs, C, Tp), C, T, Tp, out, bs_or(out_bs, C, Tp), sum, bs_or(sum_bs, C, Tp), rows);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_h_add(const unsigned short* a, size_t a_bs, const unsigned short* b, size_t b_bs, int B, int C, int T, int Tp,
+              unsigned short* out, size_t out_bs, air_stream_t stream) {
+  if (!a || !b || !out || !h_shape_ok(B, C, T, Tp)) return AIR_EINVAL;
+  // out == a / out == b with the same batch stride: the element-for-element alias.  Any other overlap of out's
+  // address range with an operand's would let one workgroup write what another still reads: refused
+  const size_t obs = bs_or(out_bs, C, Tp), span = (size_t)C * Tp;
+  const unsigned short* ops_[2] = {a, b};
+  const size_t obs_[2] = {bs_or(a_bs, C, Tp), bs_or(b_bs, C, Tp)};
+  for (int i = 0; i < 2; ++i) {
+    if (out == ops_[i] && obs == obs_[i]) continue;
+    const unsigned short* lo = ops_[i];
+    const unsigned short* hi = ops_[i] + (size_t)(B - 1) * obs_[i] + span;
+    if (out < hi && lo < out + (size_t)(B - 1) * obs + span) return AIR_EINVAL;
+  }
+  const size_t rows = (size_t)B * C;
+  hipLaunchKernelGGL(h_add_kernel, dim3(h_row_grid(rows)), dim3(NT), 0, air_stream(stream), a, bs_or(a_bs, C, Tp), b,
+                     bs_or(b_bs, C, Tp), C, T, Tp, out, bs_or(out_bs, C, Tp), rows);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_h_relu_mask_rowsum(const unsigned short* x, size_t x_bs, int B, int C, int T, int Tp, unsigned short* dx,
+                           size_t dx_bs, float* rowsum_or_null, air_stream_t stream) {
+  if (!x || !dx || x == dx || !h_shape_ok(B, C, T, Tp)) return AIR_EINVAL;
+  const size_t rows = (size_t)B * C;
+  hipLaunchKernelGGL(h_relu_mask_rowsum_kernel, dim3(h_row_grid(rows)), dim3(NT), 0, air_stream(stream), x,
+                     bs_or(x_bs, C, Tp), C, T, Tp, dx, bs_or(dx_bs, C, Tp), rowsum_or_null, rows);
   AIR_CHECK_LAUNCH();
   return AIR_OK;
 }

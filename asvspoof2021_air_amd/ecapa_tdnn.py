@@ -20,7 +20,9 @@ Layout choices that remove the reference's copies:
     write bf16; BatchNorm / SE / pooling read bf16, compute in fp32 and round each stored value once.  The tensors a
     torch.autocast(bfloat16) run of the reference holds in bf16 are the same; conv1 (K = 5, fp32 input), the
     statistics, the SE and pooled vectors, fc6 and every parameter / gradient stay fp32 (oracle/ecapa.py,
-    bf16="resident", states each rounding);
+    bf16="resident", states each rounding).  ``set_compute_dtype("bf16", variants=True)`` opens this path to the
+    constructor options ``context=False`` / ``summed=True`` (the reference's lfcc_ecapa512c{t,f}s{t,f} systems;
+    tests/ecapa_resident_variants_oracle.py states their roundings);
   * "bf16c" (rounds 1-2): bf16 COMPUTE only - the same contractions on the bf16 matrix cores, operands rounded as
     they are staged, but every tensor fp32 in HBM (plus bf16 operand copies for the weight gradients).
 """
@@ -167,7 +169,8 @@ class Res2Net2(HipModel):
         self.layer4 = nn.Conv1d(3 * C, 1536, kernel_size=1)
         self.instancenorm = nn.InstanceNorm1d(self.n_mfcc)  # constructed, never applied (:120)
         # context=False / summed=True (round 6; the reference's own score files lfcc_ecapa512c{t,f}s{t,f}_* were made with
-        # them): served by the fp32 path; the bf16 paths are built for the trainer's defaults (main_train.py:167)
+        # them): served by the fp32 path and, on request (set_compute_dtype("bf16", variants=True)), by the bf16-resident
+        # one; "bf16c" is built for the trainer's defaults (main_train.py:167)
         attn_input = 1536 * 3 if self.context else 1536  # :126-129
         # 'ASP' (:133-134): ONE attention weight per frame, shared by the 1536 channels.  Served (fp32 path) by the ECA
         # kernels on the layer's weight row repeated 1536 times - every channel then carries the same logits, which is
@@ -187,6 +190,7 @@ class Res2Net2(HipModel):
         self.bn7 = nn.BatchNorm1d(nOut)
         self.C = C
         self.compute_dtype = "fp32"
+        self.bf16_variants = False  # set_compute_dtype("bf16", variants=True)
         # weight gradients on a side HIP stream (they feed nothing until the optimiser): the MFMA-bound GEMMs and the
         # small K = 3 kernels overlap the HBM-bound BatchNorm / pooling backward passes of the main stream.  A captured
         # hipGraph keeps them on the main stream: its fork / join pairs replay slower (profiles/README.md).
@@ -200,10 +204,15 @@ class Res2Net2(HipModel):
         # fused launch is 29.9 us where conv 14.8 + apply 9.4 were 24.2) - so forward on, backward off
         self.fuse_tap_prologue = int(os.environ.get("AIR_TAP_PROLOGUE", "1"))
 
-    def set_compute_dtype(self, dtype):
+    def set_compute_dtype(self, dtype, variants=False):
+        """variants=True (with "bf16" only): the constructor options context=False / summed=True (encoder_type 'ECA')
+        run bf16-resident too instead of refusing; the default options run the same launches either way."""
         if dtype not in ("fp32", "bf16", "bf16c"):
             raise ValueError("compute_dtype must be 'fp32', 'bf16' or 'bf16c', got %r" % (dtype,))
+        if variants and dtype != "bf16":
+            raise ValueError("variants=True is an option of compute_dtype 'bf16' (the bf16-resident path), got %r" % (dtype,))
         self.compute_dtype = dtype
+        self.bf16_variants = bool(variants)
         return self
 
     def check_input(self, x):
@@ -267,9 +276,18 @@ class Res2Net2(HipModel):
     def _forward_impl(self, x, save):
         bf = self.compute_dtype == "bf16c"
         if (not self.context or self.summed or self.encoder_type != "ECA") and self.compute_dtype != "fp32":
-            raise _hip.AirError("Res2Net2(context=%s, summed=%s, encoder_type=%r): the non-default options run in "
-                                "compute_dtype 'fp32' (the bf16 paths are built for main_train.py:167's defaults)" % (
-                                    self.context, self.summed, self.encoder_type))
+            # (a module pickled before the keyword existed has no flag: off)
+            if not (self.compute_dtype == "bf16" and getattr(self, "bf16_variants", False) and self.encoder_type == "ECA"):
+                raise _hip.AirError("Res2Net2(context=%s, summed=%s, encoder_type=%r): the non-default options run in "
+                                    "compute_dtype 'fp32', and context / summed with encoder_type 'ECA' bf16-resident on "
+                                    "request: set_compute_dtype('bf16', variants=True) (the bf16 paths are built for "
+                                    "main_train.py:167's defaults)" % (self.context, self.summed, self.encoder_type))
+            if oh.tp(x.shape[2]) > oh.max_tp():  # no 'bf16c' to fall back on: that mode does not serve these options
+                raise _hip.AirError("bf16-resident ECAPA takes utterances of at most %d frames (got T = %d) and "
+                                    "Res2Net2(context=%s, summed=%s) has no 'bf16c' path to run longer ones on: use "
+                                    "set_compute_dtype('fp32') for this input" % (
+                                        oh.max_tp(), x.shape[2], self.context, self.summed))
+            return self._forward_h(x, save)
         if self.compute_dtype == "bf16":
             if oh.tp(x.shape[2]) <= oh.max_tp():
                 return self._forward_h(x, save)
@@ -605,8 +623,9 @@ class Res2Net2(HipModel):
         r = oh.conv_pointwise(x, w, T, bias=bias, bias_bc=bias_bc, relu=True)
         return r, self._bn_h(r, T, bn, training)
 
-    def _block_fwd_h(self, blk, inp, out, T, training, save):
+    def _block_fwd_h(self, blk, inp, out, T, training, save, sum_out=None):
         """Bottle2neck (ecapa_tdnn.py:64-95) on resident rows.  ``inp`` / ``out`` may be channel-slice views.
+        sum_out (summed=True, :163-166): receives bf16(out + inp), the next block's input, from the SE pass.
         o1 = bn1(relu(conv1(inp))) is written into the buffer that becomes the concat: branch i's BatchNorm output
         replaces o1's slice i after that slice has been consumed, the pass-through group (:85) never moves."""
         B, C, Tp = inp.shape
@@ -657,7 +676,10 @@ class Res2Net2(HipModel):
         stS = ops.bn_coeffs(z1.view(B, -1, 1), se[3], training)
         z1n = ops.bn_apply(z1.view(B, -1, 1), stS[2], stS[3]).view(B, -1)
         z2 = ops.linear_fwd(z1n, det(se[4].weight).view(se[4].out_channels, -1), det(se[4].bias))
-        oh.se_scale_fwd(o3, z2, inp, T, out)
+        if sum_out is None:
+            oh.se_scale_fwd(o3, z2, inp, T, out)
+        else:
+            oh.se_scale_fwd_sum(o3, z2, inp, T, out, sum_out)
         if save:
             return dict(blk=blk, inp=inp, r1=r1, st1=st1, t=t_list, r=r_list, st=st_list, cat=cat, r3=r3, st3=st3,
                         o3=o3, m=m, z1=z1, stS=stS, z1n=z1n, z2=z2)
@@ -684,21 +706,33 @@ class Res2Net2(HipModel):
         r0, st0 = self._pw_bn_h(xcol, self._conv1_matrix(), T, det(self.conv1.bias), self.bn1, training)
         h = oh.bn_apply(r0, T, st0[2], st0[3])
         cat123 = oh.rows(B, 3 * C, T, dev)
-        blocks = []
+        blocks, sums = [], []
         inp = h
         for k, blk in enumerate((self.layer1, self.layer2, self.layer3)):
             out = cat123[:, k * C:(k + 1) * C]
-            blocks.append(self._block_fwd_h(blk, inp, out, T, training, save))
-            inp = out
+            if self.summed and k < 2:
+                # :163-166: the next block reads x + x1 (+ x2), the running sum s_k = bf16(s_{k-1} + x_k) - a resident
+                # tensor of its own, written by the pass that stores x_k
+                sums.append(oh.rows(B, C, T, dev))
+                blocks.append(self._block_fwd_h(blk, inp, out, T, training, save, sum_out=sums[k]))
+                inp = sums[k]
+            else:
+                blocks.append(self._block_fwd_h(blk, inp, out, T, training, save))
+                inp = out
         x4 = oh.conv_pointwise(cat123, det(self.layer4.weight), T, bias=det(self.layer4.bias), relu=True)  # :172-173
-        mean, std = oh.row_stats(x4, T, True, 1e-4)  # context statistics (:178)
-        ctx = torch.cat((mean, std), 1)
         a0, a3 = self.attention[0], self.attention[3]
-        w0 = det(a0.weight).view(128, -1)
-        w_x = ops.add_strided(torch.empty((128, 1, 1536), device=dev), w0[:, :1536].unsqueeze(1)).view(128, 1536, 1)
-        w_c = ops.add_strided(torch.empty((128, 1, 3072), device=dev), w0[:, 1536:].unsqueeze(1)).view(128, 3072)
-        ctxb = ops.linear_fwd(ctx, w_c, None)  # (B,128): W[:,1536:] @ [mean; std], a per-utterance bias
-        a1, stA = self._pw_bn_h(x4, w_x, T, det(a0.bias), self.attention[2], training, bias_bc=ctxb)  # attention.0 + ReLU
+        if self.context:
+            mean, std = oh.row_stats(x4, T, True, 1e-4)  # context statistics (:178)
+            ctx = torch.cat((mean, std), 1)
+            w0 = det(a0.weight).view(128, -1)
+            w_x = ops.add_strided(torch.empty((128, 1, 1536), device=dev), w0[:, :1536].unsqueeze(1)).view(128, 1536, 1)
+            w_c = ops.add_strided(torch.empty((128, 1, 3072), device=dev), w0[:, 1536:].unsqueeze(1)).view(128, 3072)
+            ctxb = ops.linear_fwd(ctx, w_c, None)  # (B,128): W[:,1536:] @ [mean; std], a per-utterance bias
+            a1, stA = self._pw_bn_h(x4, w_x, T, det(a0.bias), self.attention[2], training, bias_bc=ctxb)  # attention.0 + ReLU
+        else:  # :179-180: global_x = x - the layer's own (128, 1536, 1) weight on x4, no statistics anywhere
+            mean = std = ctx = w_c = None
+            w_x = det(a0.weight)
+            a1, stA = self._pw_bn_h(x4, w_x, T, det(a0.bias), self.attention[2], training)
         a1n = oh.bn_apply(a1, T, stA[2], stA[3])
         wts = oh.conv_pointwise(a1n, det(a3.weight), T, bias=det(a3.bias))  # logits -> softmax weights below
         pooled = oh.asp_fwd(x4, wts, T)  # :184-187 (mu | sg)
@@ -715,9 +749,12 @@ class Res2Net2(HipModel):
         if save:
             if not training:
                 raise NotImplementedError("backward through eval-mode BatchNorm is not on the hot path")
-            S = dict(resident=True, T=T, x=x, xcol=xcol, r0=r0, st0=st0, h=h, cat123=cat123, blocks=blocks, x4=x4, mean=mean, std=std,
-                     ctx=ctx, w_x=w_x, w_c=w_c, a1=a1, stA=stA, a1n=a1n, wts=wts, pooled=pooled, st5=st5, p5=p5,
-                     feat=feat, o7=o7, st7=st7)
+            S = dict(resident=True, T=T, x=x, xcol=xcol, r0=r0, st0=st0, h=h, cat123=cat123, blocks=blocks, x4=x4,
+                     w_x=w_x, a1=a1, stA=stA, a1n=a1n, wts=wts, pooled=pooled, st5=st5, p5=p5, feat=feat, o7=o7, st7=st7)
+            if self.context:
+                S.update(mean=mean, std=std, ctx=ctx, w_c=w_c)
+            if self.summed:
+                S.update(s_1=sums[0], s_2=sums[1])
         ops.bn_flush()
         return feat, out, S
 
@@ -833,33 +870,50 @@ class Res2Net2(HipModel):
         stA = S["stA"]
         da1 = oh.bn_bwd(S["a1"], da1n, T, stA[0], stA[1], det(self.attention[2].weight), G["attention.2.weight"],
                         G["attention.2.bias"], dx=da1n, dbias=G["attention.0.bias"])
-        gw0 = G["attention.0.weight"].view(128, -1)  # (128, 4608)
-
-        def att0_wgrad():
-            dwx = oh.conv_wgrad(x4, da1, T, torch.empty((128, 1536, 1), device=dev, dtype=torch.float32))
-            ops.add_strided(gw0[:, :1536].unsqueeze(1), dwx.view(128, 1, 1536))
-
-        on_side(att0_wgrad, da1)
-        oh.conv_pointwise(da1, S["w_x"], T, dgrad=True, acc=dx4, out=dx4)
-        dctxb = oh.row_stats(da1, T, want_std=False)[0] * float(T)  # (B,128): sum over time of d(a1)
-        dctx, dwc, _ = ops.linear_bwd(S["ctx"], S["w_c"], dctxb.contiguous(), True, need_db=False)
-        ops.add_strided(gw0[:, 1536:].unsqueeze(1), dwc.view(128, 1, 3072))
-        dmean = dctx[:, :1536].contiguous()
-        dstd = dctx[:, 1536:].contiguous()
         rows = torch.empty((B, x4.shape[1]), device=dev, dtype=torch.float32)
-        oh.row_stats_bwd(x4, T, S["mean"], S["std"], dmean, dstd, dx4, accumulate=True, relu_mask=True, rowsum=rows)
+        if S.get("ctx") is not None:
+            gw0 = G["attention.0.weight"].view(128, -1)  # (128, 4608)
+
+            def att0_wgrad():
+                dwx = oh.conv_wgrad(x4, da1, T, torch.empty((128, 1536, 1), device=dev, dtype=torch.float32))
+                ops.add_strided(gw0[:, :1536].unsqueeze(1), dwx.view(128, 1, 1536))
+
+            on_side(att0_wgrad, da1)
+            oh.conv_pointwise(da1, S["w_x"], T, dgrad=True, acc=dx4, out=dx4)
+            dctxb = oh.row_stats(da1, T, want_std=False)[0] * float(T)  # (B,128): sum over time of d(a1)
+            dctx, dwc, _ = ops.linear_bwd(S["ctx"], S["w_c"], dctxb.contiguous(), True, need_db=False)
+            ops.add_strided(gw0[:, 1536:].unsqueeze(1), dwc.view(128, 1, 3072))
+            dmean = dctx[:, :1536].contiguous()
+            dstd = dctx[:, 1536:].contiguous()
+            oh.row_stats_bwd(x4, T, S["mean"], S["std"], dmean, dstd, dx4, accumulate=True, relu_mask=True, rowsum=rows)
+        else:
+            # context=False: the (128, 1536) contraction is the layer's whole weight gradient; d(x4) = bf16(bf16(pooling)
+            # + attention.0's dgrad), then layer4's ReLU mask and the bias row sums in a pass that reads no statistics
+            on_side(lambda: oh.conv_wgrad(x4, da1, T, G["attention.0.weight"]), da1)
+            oh.conv_pointwise(da1, S["w_x"], T, dgrad=True, acc=dx4, out=dx4)
+            oh.relu_mask_rowsum(x4, T, dx4, rowsum=rows)
         ops.sum_rows(rows, out=G["layer4.bias"])
         on_side(lambda: oh.conv_wgrad(S["cat123"], dx4, T, G["layer4.weight"]), dx4)
         sch.grads_final_from("layer4.weight")
         dcat123 = oh.conv_pointwise(dx4, det(self.layer4.weight), T, dgrad=True)
         dnext = None
+        dblk = dcat123[:, 2 * C:]  # block 3 reads its slice of the concat gradient in place
         for k in (2, 1, 0):
-            # d(block k output) = its slice of the concat gradient + d(block k + 1 input): block k + 1's last dgrad
-            # already added this block's slice (add2); block 3 reads its slice in place
-            dblk = dcat123[:, k * C:(k + 1) * C] if dnext is None else dnext
-            add2 = dcat123[:, (k - 1) * C:k * C] if k > 0 else None
-            dnext = self._block_bwd_h(S["blocks"][k], dblk, T, G, "layer%d." % (k + 1), add2, on_side)
+            if not self.summed:
+                # d(block k output) = its slice of the concat gradient + d(block k + 1 input): block k + 1's last dgrad
+                # already added this block's slice (add2)
+                add2 = dcat123[:, (k - 1) * C:k * C] if k > 0 else None
+                dblk = dnext = self._block_bwd_h(S["blocks"][k], dblk, T, G, "layer%d." % (k + 1), add2, on_side)
+                sch.grads_final_from("layer%d.conv1.weight" % (k + 1))
+                continue
+            # summed=True (:163-166), blocks with inputs s_{k-1} (s_0 = h), s_k = s_{k-1} + x_k: d s_{k-1} = bf16(conv1_k's
+            # dgrad + d x_k + d s_k) - the block's last dgrad with acc = d x_k (the residual) and acc2 = d s_k; then
+            # d x_{k-1} = bf16(concat slice + d s_{k-1}), written over the slice (nothing else reads it: in place)
+            dnext = self._block_bwd_h(S["blocks"][k], dblk, T, G, "layer%d." % (k + 1), dnext, on_side)
             sch.grads_final_from("layer%d.conv1.weight" % (k + 1))
+            if k > 0:
+                dblk = dcat123[:, (k - 1) * C:k * C]
+                oh.add(dblk, dnext, T, out=dblk)
         st0 = S["st0"]
         dc0 = oh.bn_bwd(S["r0"], dnext, T, st0[0], st0[1], det(self.bn1.weight), G["bn1.weight"], G["bn1.bias"], dx=dnext,
                         dbias=G["conv1.bias"])

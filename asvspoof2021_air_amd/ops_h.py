@@ -328,6 +328,32 @@ def se_scale_fwd(x, z, res, T, out):
     return out
 
 
+def se_scale_fwd_sum(x, z, res, T, out, sum_out):
+    """``se_scale_fwd`` + the running sum of summed=True from the same pass: sum_out = bf16(stored out + res)."""
+    B, C, Tp = x.shape
+    xp, xb = hv(x)
+    rp, rb = hv(res)
+    op, ob = hv(out)
+    sp, sb = hv(sum_out)
+    _hip.check(_hip.lib().air_h_se_scale_fwd_sum(xp, csz(xb), dptr(z), rp, csz(rb), ci(B), ci(C), ci(T), ci(Tp), op, csz(ob),
+                                                 sp, csz(sb), stream()), "air_h_se_scale_fwd_sum")
+    return out, sum_out
+
+
+def add(a, b, T, out=None):
+    """out = bf16(a + b) on resident rows / channel slices; out may be a or b (in place), default a fresh tensor."""
+    B, C, Tp = a.shape
+    if tuple(b.shape) != (B, C, Tp):
+        raise _hip.AirError("add: operands of %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if out is None:
+        out = torch.empty((B, C, Tp), device=a.device, dtype=torch.int16)
+    ap, ab = hv(a)
+    bp, bb = hv(b)
+    op, ob = hv(out)
+    _hip.check(_hip.lib().air_h_add(ap, csz(ab), bp, csz(bb), ci(B), ci(C), ci(T), ci(Tp), op, csz(ob), stream()), "air_h_add")
+    return out
+
+
 def se_scale_bwd(x, z, dout, T):
     B, C, Tp = x.shape
     dx = torch.empty((B, C, Tp), device=x.device, dtype=torch.int16)
@@ -356,6 +382,17 @@ def row_stats_bwd(x, T, mean, std, dmean, dstd, dx, accumulate=True, clamp_min=1
                                               dptr(dstd, allow_none=True), cf(clamp_min), dptr(dx, torch.int16),
                                               ci(1 if accumulate else 0), ci(1 if relu_mask else 0),
                                               dptr(rowsum, allow_none=True), stream()), "air_h_row_stats_bwd")
+    return dx
+
+
+def relu_mask_rowsum(x, T, dx, rowsum=None):
+    """dx = bf16(dx) where x > 0, else 0 (in place); rowsum (B, C) fp32 = sum over t of the stored dx.  The
+    context=False counterpart of ``row_stats_bwd(accumulate=True, relu_mask=True)``: reads no statistics."""
+    B, C, Tp = x.shape
+    xp, xb = hv(x)
+    dp, db = hv(dx)
+    _hip.check(_hip.lib().air_h_relu_mask_rowsum(xp, csz(xb), ci(B), ci(C), ci(T), ci(Tp), dp, csz(db),
+                                                 dptr(rowsum, allow_none=True), stream()), "air_h_relu_mask_rowsum")
     return dx
 
 

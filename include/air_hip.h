@@ -744,6 +744,19 @@ int air_h_se_scale_fwd(const unsigned short* x, size_t x_bs, const float* z, con
                        int B, int C, int T, int Tp, unsigned short* out, size_t out_bs, air_stream_t stream);
 int air_h_se_scale_bwd(const unsigned short* x, size_t x_bs, const float* z, const unsigned short* dout, size_t dout_bs,
                        int B, int C, int T, int Tp, unsigned short* dx, size_t dx_bs, float* dz, air_stream_t stream);
+/* summed=True (ecapa_tdnn.py:163-166, "x2 = self.layer2(x + x1)"): air_h_se_scale_fwd with a second output, the running
+ * sum of the block inputs, from the same pass - out as above (the same bits), sum = bf16(out + res) on the STORED out
+ * (the bf16 + bf16 add of the reference under autocast).  sum: rows or a channel slice, distinct from x / res / out.
+ * AIR_EINVAL for rows beyond the register cache (Tp > 2048), like every row kernel here. */
+int air_h_se_scale_fwd_sum(const unsigned short* x, size_t x_bs, const float* z, const unsigned short* res, size_t res_bs,
+                           int B, int C, int T, int Tp, unsigned short* out, size_t out_bs, unsigned short* sum,
+                           size_t sum_bs, air_stream_t stream);
+/* out = bf16(a + b), frames >= T zero: the gradient joins of summed=True (the backward of :163-166's adds: d x_k = its
+ * slice of the concat gradient + d(x + x1 [+ x2])).  a, b, out: rows or channel slices; out may be a or b itself
+ * (element for element, the same batch stride); any other overlap of out's address range with an operand's is refused
+ * (AIR_EINVAL), as is Tp > 2048. */
+int air_h_add(const unsigned short* a, size_t a_bs, const unsigned short* b, size_t b_bs, int B, int C, int T, int Tp,
+              unsigned short* out, size_t out_bs, air_stream_t stream);
 /* Context statistics (ecapa_tdnn.py:178) of a dense bf16 tensor and their backward folded into dx
  * (dx = bf16(dx + ...), ReLU mask of layer4's output, rowsum of the stored values): air_row_stats[_bwd]. */
 int air_h_row_stats(const unsigned short* x, int B, int C, int T, int Tp, float* mean, float* std_or_null,
@@ -751,6 +764,12 @@ int air_h_row_stats(const unsigned short* x, int B, int C, int T, int Tp, float*
 int air_h_row_stats_bwd(const unsigned short* x, int B, int C, int T, int Tp, const float* mean, const float* std_,
                         const float* dmean, const float* dstd, float clamp_min, unsigned short* dx, int accumulate,
                         int relu_mask, float* rowsum_or_null, air_stream_t stream);
+/* context=False (ecapa_tdnn.py:179-180, "global_x = x"): no statistics feed attention.0, so the backward of layer4's
+ * ReLU (:173) is the mask alone - dx = bf16(dx) where x > 0, else 0, in place, and rowsum (B * C, may be NULL) = sum_t
+ * of the stored dx: the bits of air_h_row_stats_bwd(accumulate = 1, relu_mask = 1) with zero dmean / dstd, without
+ * reading mean / std.  x, dx: rows or channel slices, distinct.  AIR_EINVAL for Tp > 2048. */
+int air_h_relu_mask_rowsum(const unsigned short* x, size_t x_bs, int B, int C, int T, int Tp, unsigned short* dx,
+                           size_t dx_bs, float* rowsum_or_null, air_stream_t stream);
 /* Attentive statistics pooling (ecapa_tdnn.py:143-185): logits (bf16) -> w = bf16(softmax_T) in place; [mu | sg]
  * from the STORED w.  bwd: dx written (bf16), w overwritten with bf16(d logits), rowsum of the stored d logits. */
 int air_h_asp_fwd(const unsigned short* x, unsigned short* logits_to_w, int B, int C, int T, int Tp, float* out,

@@ -584,6 +584,25 @@ __global__ __launch_bounds__(256) void wino_conv_kernel(WinoArgs a) {
 #define W2_TX_AT 6   // MFMA slots after which the next k-step's patch / dy transforms are placed
 #define W2_TG_AT 10
 #endif
+// k-step experiments (profiles/wino_wgrad_kstep.md); W2_EARLY_SWAP = W2_STAGE_AHEAD = 0 is the kernel before them
+#ifndef W2_HALF_ROWS
+#define W2_HALF_ROWS 1   // A/B: 0 = every stage issues all 16 products (rounds 1 - 3)
+#endif
+#ifndef W2_PLAIN_XF
+#define W2_PLAIN_XF 0    // transforms as v_add_f32 / v_sub_f32 instead of v_pk_add_f32 (bit-identical)
+#endif
+#ifndef W2_EARLY_SWAP
+#define W2_EARLY_SWAP 1  // buffer-swap barrier behind k-step 6; the next stage's first operands under k-step 7's MFMAs
+#endif
+#ifndef W2_STAGE_AHEAD
+#define W2_STAGE_AHEAD 1 // stage geometry stepped, branch-free, one stage ahead in three MFMA gaps of k-step 4; one
+#endif                   // half-row test per k-step and none per DMA.  0: divided out of the stage number at its head
+#ifndef W2_TRACE
+#define W2_TRACE 0       // diagnostic build: cycle stamps (tools/wino_wgrad_kstep.py); never the default library
+#endif
+#ifndef W2_EXP_NOXF
+#define W2_EXP_NOXF 0    // timing-only build: both transforms compiled out, results garbage
+#endif
 constexpr int WG_SEG = 16;                    // tiles per stage
 constexpr int WG_XC = 40;                     // staged x columns per row: image cols 32 seg - 4 ...
 constexpr int WG_XP = 4 * WG_XC + 2;          // floats per channel (odd half: conflict-free b64 / b32x2)
@@ -601,6 +620,9 @@ struct WinoWgArgs {
   int TH, NTS;       // tile rows, tile-row segments per row
   int nseg;          // B * TH * NTS
   int ncob, ncib, nsplit;
+#if W2_TRACE
+  long long* trace;  // [workgroup][16] cycle buckets, or null
+#endif
 };
 
 // (x + y, x - y) of one register pair
@@ -610,6 +632,34 @@ __device__ __forceinline__ f32x2 pk_sumdiff(f32x2 q) {
                : "=v"(r) : "v"(q));
   return r;
 }
+#if W2_PLAIN_XF
+// the same sums on single registers: asm, so that the vectoriser cannot pair them up again
+__device__ __forceinline__ float f_add(float x, float y) {
+  float r;
+  asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+__device__ __forceinline__ float f_sub(float x, float y) {
+  float r;
+  asm volatile("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+__device__ __forceinline__ f32x2 w2_add(f32x2 x, f32x2 y) { return f32x2{f_add(x[0], y[0]), f_add(x[1], y[1])}; }
+__device__ __forceinline__ f32x2 w2_sub(f32x2 x, f32x2 y) { return f32x2{f_sub(x[0], y[0]), f_sub(x[1], y[1])}; }
+__device__ __forceinline__ f32x2 w2_sumdiff(f32x2 q) { return f32x2{f_add(q[0], q[1]), f_sub(q[0], q[1])}; }
+__device__ __forceinline__ f32x2 w2_col01(f32x2 lo, f32x2 hi) {
+  return f32x2{f_sub(lo[0], hi[0]), f_add(lo[1], hi[0])};
+}
+__device__ __forceinline__ f32x2 w2_col23(f32x2 lo, f32x2 hi) {
+  return f32x2{f_sub(hi[0], lo[1]), f_sub(lo[1], hi[1])};
+}
+#else
+#define w2_add pk_add
+#define w2_sub pk_sub
+#define w2_sumdiff pk_sumdiff
+#define w2_col01 pk_col01
+#define w2_col23 pk_col23
+#endif
 template <int MIMM>
 __device__ __forceinline__ void dma16_at(i32x4 rsrc, unsigned soff, unsigned mbase, unsigned v0) {
   asm volatile("s_add_i32 m0, %1, %4\n\ts_nop 0\n\t"
@@ -651,11 +701,14 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
 
   // stage geometry -> per-lane source offsets (one VGPR each) and the wave's channel bases
   int edge_col = -1;  // staged column of image column W if a valid tile of the stage sees it
+  bool n_half = false, cur_half = false;  // HALF (below) of the stage being staged / being multiplied
+#if !W2_STAGE_AHEAD
   auto set_stage = [&](int s, unsigned& vx, unsigned& vd, unsigned& xs, unsigned& dsf, int& ecol) {
     const int seg = s % a.NTS;
     const int r = s / a.NTS;
     const int th = r % a.TH;
     const int b = r / a.TH;
+    n_half = W2_HALF_ROWS && 2 * th + 1 >= a.H;
     {
       const int row = 2 * th - 1 + lane / 10, col0 = 32 * seg - 4 + 4 * (lane % 10);
       const bool ok = lane < 40 && row >= 0 && row < a.H && col0 >= 0 && col0 < a.W;
@@ -670,6 +723,44 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
     const int wc = a.W - (32 * seg - 4);  // staged column of image column W
     ecol = (wc >= 4 && wc < WG_XC) ? wc : -1;
   };
+#else
+  // The same geometry without its five divisions by run-time values and without branches: the stages are visited
+  // in order, so (seg, th, b) are stepped with carries; the lane's share of the offsets is computed once; the rest
+  // comes in three pieces (x offsets, dy offsets, scalars) that fit the shadow of an MFMA each.  `live` = the stage
+  // exists: beyond the workgroup's last stage every lane is out of range, and the surplus DMAs bring zeros into the
+  // buffer that nobody reads again.
+  int q_seg = s0 % a.NTS, q_th = (s0 / a.NTS) % a.TH, q_b = (s0 / a.NTS) / a.TH;  // the next stage_x's stage
+  const int xl_row = lane / 10, xl_col = 4 * (lane % 10);
+  const unsigned vx_lane = (unsigned)((xl_row * a.W + xl_col) * 4), vd_lane = (unsigned)((half * a.W + l31) * 4);
+  const unsigned xs_wave = __builtin_amdgcn_readfirstlane((unsigned)((cib * 64 + wave * 16) * HWi) * 4u);
+  const unsigned ds_wave = __builtin_amdgcn_readfirstlane((unsigned)((cob * 64 + wave * 16) * HWi) * 4u);
+  const unsigned xs_img = (unsigned)(a.Cin * HWi) * 4u, ds_img = (unsigned)(a.Cout * HWi) * 4u;
+  int g_seg = 0, g_th = 0, g_b = 0;
+  bool g_live = false;
+  auto stage_x = [&](bool live, unsigned& vx) {
+    const int seg = q_seg, th = q_th, b = q_b;
+    if (++q_seg == a.NTS) {
+      q_seg = 0;
+      if (++q_th == a.TH) { q_th = 0; ++q_b; }
+    }
+    g_seg = seg; g_th = th; g_b = b; g_live = live;
+    const int row0 = 2 * th - 1, col0 = 32 * seg - 4;
+    const bool ok = (int)live & (int)(lane < 40) & (int)((unsigned)(row0 + xl_row) < (unsigned)a.H) &
+                    (int)((unsigned)(col0 + xl_col) < (unsigned)a.W);
+    vx = ok ? (unsigned)((row0 * a.W + col0) * 4) + vx_lane : OOB;
+  };
+  auto stage_d = [&](unsigned& vd) {
+    const bool ok = (int)g_live & (int)(2 * g_th + half < a.H) & (int)(32 * g_seg + l31 < a.W);
+    vd = ok ? (unsigned)((2 * g_th * a.W + 32 * g_seg) * 4) + vd_lane : OOB;
+  };
+  auto stage_s = [&](unsigned& xs, unsigned& dsf, int& ecol) {
+    xs = xs_wave + (unsigned)g_b * xs_img;
+    dsf = ds_wave + (unsigned)g_b * ds_img;
+    const int wc = a.W - (32 * g_seg - 4);  // staged column of image column W
+    ecol = (g_live && wc >= 4 && wc < WG_XC) ? wc : -1;
+    n_half = W2_HALF_ROWS && 2 * g_th + 1 >= a.H;
+  };
+#endif
 
   // DMA unit u (0 .. 31) of the stage being staged into buffer `buf`: 16 x channels, 16 dy channels
   unsigned n_vox = OOB, n_vod = OOB, n_xs = 0, n_ds = 0, mXn = 0, mDn = 0;
@@ -711,24 +802,39 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
     g[1] = *reinterpret_cast<const f32x2*>(pd + 32);
   };
   auto transform_x = [&](int set) {  // patch -> V[set]
-    tl[0] = pk_sub(d[0], d[4]); th2[0] = pk_sub(d[1], d[5]);
-    tl[1] = pk_add(d[2], d[4]); th2[1] = pk_add(d[3], d[5]);
-    tl[2] = pk_sub(d[4], d[2]); th2[2] = pk_sub(d[5], d[3]);
-    tl[3] = pk_sub(d[2], d[6]); th2[3] = pk_sub(d[3], d[7]);
+#if W2_EXP_NOXF
+    (void)tl; (void)th2;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {  // the LDS reads and their wait stay, the adds go; V is whatever the registers hold
+      asm volatile("" :: "v"(d[i]));
+      asm volatile("" : "=v"(V[set][i]));
+    }
+#else
+    tl[0] = w2_sub(d[0], d[4]); th2[0] = w2_sub(d[1], d[5]);
+    tl[1] = w2_add(d[2], d[4]); th2[1] = w2_add(d[3], d[5]);
+    tl[2] = w2_sub(d[4], d[2]); th2[2] = w2_sub(d[5], d[3]);
+    tl[3] = w2_sub(d[2], d[6]); th2[3] = w2_sub(d[3], d[7]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      V[set][2 * i] = pk_col01(tl[i], th2[i]);
-      V[set][2 * i + 1] = pk_col23(tl[i], th2[i]);
+      V[set][2 * i] = w2_col01(tl[i], th2[i]);
+      V[set][2 * i + 1] = w2_col23(tl[i], th2[i]);
     }
+#endif
   };
   auto transform_g = [&](int set) {  // dy tile -> Q[set], Sd[set]
     // G' g G'^T without its 1/2 factors (they are applied in the output transform)
+#if W2_EXP_NOXF
+    asm volatile("" :: "v"(g[0]), "v"(g[1]));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("" : "=v"(Q[set][i]), "=v"(Sd[set][i]));
+#else
     Q[set][0] = g[0];
-    Q[set][1] = pk_add(g[0], g[1]);
-    Q[set][2] = pk_sub(g[0], g[1]);
+    Q[set][1] = w2_add(g[0], g[1]);
+    Q[set][2] = w2_sub(g[0], g[1]);
     Q[set][3] = g[1];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) Sd[set][i] = pk_sumdiff(Q[set][i]);
+    for (int i = 0; i < 4; ++i) Sd[set][i] = w2_sumdiff(Q[set][i]);
+#endif
   };
   auto opA = [&](int set, int i, int j) -> float {
     return j == 0 ? Q[set][i][0] : (j == 1 ? Sd[set][i][0] : (j == 2 ? Sd[set][i][1] : Q[set][i][1]));
@@ -744,16 +850,50 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
     }
   };
 
+#if W2_TRACE
+  // cycles between consecutive stamps, added into the bucket the stamp names (wave-uniform: scalar registers)
+  long long t_acc[14], t_last = __builtin_amdgcn_s_memtime();
+#pragma unroll
+  for (int i = 0; i < 14; ++i) t_acc[i] = 0;
+  auto stamp = [&](int bucket) {
+    const long long t = __builtin_amdgcn_s_memtime();
+    t_acc[bucket] += t - t_last;
+    t_last = t;
+  };
+  enum { T_PRO = 0, T_HEAD = 1, T_KS = 2, T_WAIT = 10, T_BAR = 11, T_EPI = 12, T_NST = 13 };
+#define W2_STAMP(B_) stamp(B_)
+#else
+#define W2_STAMP(B_)
+#endif
   if (s0 < s1) {
     // prologue: stage s0 whole, wait, fix, first operands
+#if W2_STAGE_AHEAD
+    stage_x(true, n_vox);
+    stage_d(n_vod);
+    stage_s(n_xs, n_ds, n_edge);
+#else
     set_stage(s0, n_vox, n_vod, n_xs, n_ds, n_edge);
+#endif
     mXn = mX0; mDn = mD0;
 #pragma unroll
     for (int u = 0; u < 32; ++u) dma_unit(u);
     edge_col = n_edge;
+    cur_half = n_half;
+#if W2_STAGE_AHEAD
+    stage_x(s0 + 1 < s1, n_vox);  // the DMAs above hold their operands: stage s0 + 1 may follow
+    stage_d(n_vod);
+    stage_s(n_xs, n_ds, n_edge);
+#endif
     dma_wait();
     __syncthreads();
+#if W2_EARLY_SWAP
+    if (edge_col >= 0) fix_edge(lds, edge_col);
+    ld(lds, 0);
+    transform_x(0);
+    transform_g(0);
+#endif
   }
+  W2_STAMP(T_PRO);
   // HALF: the stage lies in the last tile row of an image with an odd row count - the dy tiles' second row is beyond
   // the image (zeros), so row 3 of G' g G'^T is zero and the four products M[3][*] with it: 12 MFMAs per k-step
   // instead of 16 (F(3x3, 1x2) in effect).  The ResNet's 9 / 5 / 3-row maps have 1 of 5 / 3 / 2 tile rows like that:
@@ -761,63 +901,165 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
   // (a wave-uniform branch around those four MFMAs, not a second instantiation of the stage: the 256 accumulator
   // registers + 256 VGPRs are full, and a duplicated body tripled the spills - 0.31 -> 0.42 ms on layer1, which has
   // no such row at all)
-  auto stage_body = [&](auto first_tag, bool hs, int s, int cur) {
+  //
+  // Buffer swap (W2_EARLY_SWAP).  Stage s multiplies out of buffer `cur` while the DMAs of stage s + 1 fill the other
+  // one during k-steps 0 - 3.  A wave's last read of `cur` is ld(., 7), issued at the head of k-step 6 and consumed by
+  // the transforms inside it, so behind k-step 6's MFMAs every wave drains its own DMAs (vmcnt 0) and meets the others
+  // at the barrier.  Past that barrier (1) every DMA of every wave into the other buffer has landed, so k-step 7 may
+  // fix its edge cells, read its first operands and transform them under its own MFMAs, and (2) no wave reads `cur`
+  // again, so the DMAs that the next stage issues into `cur` - all of them behind this barrier in program order -
+  // cannot overtake a read.  The DMAs into the other buffer were themselves issued behind the previous stage's
+  // barrier, after that buffer's last read.  A stage thus begins with its first MFMA instead of an LDS round trip
+  // and 22 transform instructions.
+  auto mma = [&](auto first_tag, int ks, int j) {
+    constexpr bool FIRST = decltype(first_tag)::value;
+    const int cs = ks & 1;
+    if (FIRST && ks == 0)
+      acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(opA(cs, j >> 2, j & 3), V[cs][j >> 1][j & 1],
+                                                   (f32x16){0}, 0, 0, 0);
+    else
+      acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(opA(cs, j >> 2, j & 3), V[cs][j >> 1][j & 1],
+                                                   acc[j], 0, 0, 0);
+  };
+  auto stage_body = [&](auto first_tag, int s, int cur) {
     constexpr bool FIRST = decltype(first_tag)::value;
     float* bcur = lds + cur * WG_BUF;
+    const bool hs = cur_half;
+#if !W2_EARLY_SWAP
     if (edge_col >= 0) fix_edge(bcur, edge_col);
+#endif
+#if W2_STAGE_AHEAD
+    // n_* describe stage s + 1 already (prologue / k-step 4 of the stage before); k-step 4 moves them on to stage
+    // s + 2, and k-step 7 and the next stage still want these two
+    const int e_keep = n_edge;
+    const bool h_keep = n_half;
+#else
     const bool more = s + 1 < s1;
-    if (more) {
-      set_stage(s + 1, n_vox, n_vod, n_xs, n_ds, n_edge);
+    if (more) set_stage(s + 1, n_vox, n_vod, n_xs, n_ds, n_edge);
+    const int e_keep = n_edge;
+    const bool h_keep = n_half;
+#endif
+    {
       const unsigned nb = (unsigned)(cur ^ 1) * (WG_BUF * 4u);
       mXn = __builtin_amdgcn_readfirstlane(mX0 + nb);
       mDn = __builtin_amdgcn_readfirstlane(mD0 + nb);
     }
+#if !W2_EARLY_SWAP
     ld(bcur, 0);
     transform_x(0);  // the stage's first k-step: exposed; the other seven are transformed under the MFMAs before them
     transform_g(0);
+#endif
+    W2_STAMP(T_HEAD);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      const int cs = ks & 1, ns = cs ^ 1;
+      const int ns = (ks & 1) ^ 1;
       if (ks < 7) ld(bcur, ks + 1);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        // the next stage's 32 DMAs: one per second MFMA slot of the first four k-steps
-#if W2_DMA_KS == 2
-        if (ks < 2 && more) dma_unit(ks * 16 + j);
+#if W2_EARLY_SWAP
+      if (ks == 7) {  // the other buffer is complete (barrier behind k-step 6): the next stage's first operands
+        float* bnxt = lds + (cur ^ 1) * WG_BUF;
+        if (e_keep >= 0) fix_edge(bnxt, e_keep);
+        ld(bnxt, 0);
+      }
+#endif
+#if W2_STAGE_AHEAD
+      constexpr bool DMA_ON = true;  // the last stage's are out of range
 #else
-        if (ks < 4 && (j & 1) == 0 && more) dma_unit(ks * 8 + j / 2);
+      const bool DMA_ON = more;
+#endif
+      constexpr bool XF7 = W2_EARLY_SWAP != 0;  // k-step 7 transforms too (behind the last stage: unused values)
+#pragma unroll
+      for (int j = 0; j < (W2_STAGE_AHEAD ? 12 : 16); ++j) {
+        // the next stage's 32 DMAs: one per second MFMA slot of the first four k-steps
+#if W2_STAGE_AHEAD
+        // ... and, their operands free again, the geometry of the stage after it
+        if (ks == 4 && j == 1) {
+          stage_x(s + 2 < s1, n_vox);
+          // (the values are wanted one stage later: pinned, or the compiler sinks the arithmetic out of this MFMA
+          // gap to the end of the stage, where nothing hides it)
+          q_seg = __builtin_amdgcn_readfirstlane(q_seg); q_th = __builtin_amdgcn_readfirstlane(q_th);
+          q_b = __builtin_amdgcn_readfirstlane(q_b);
+          asm volatile("" : "+v"(n_vox), "+s"(q_seg), "+s"(q_th), "+s"(q_b));
+        }
+        if (ks == 4 && j == 3) {
+          stage_d(n_vod);
+          asm volatile("" : "+v"(n_vod));
+        }
+        if (ks == 4 && j == 5) {
+          stage_s(n_xs, n_ds, n_edge);
+          int nh = __builtin_amdgcn_readfirstlane((int)n_half);
+          n_xs = __builtin_amdgcn_readfirstlane(n_xs); n_ds = __builtin_amdgcn_readfirstlane(n_ds);
+          n_edge = __builtin_amdgcn_readfirstlane(n_edge);
+          asm volatile("" : "+s"(n_xs), "+s"(n_ds), "+s"(n_edge), "+s"(nh));
+          n_half = nh != 0;
+        }
+#endif
+#if W2_DMA_KS == 2
+        if (ks < 2 && DMA_ON) dma_unit(ks * 16 + j);
+#else
+        if (ks < 4 && (j & 1) == 0 && DMA_ON) dma_unit(ks * 8 + j / 2);
 #endif
         __builtin_amdgcn_sched_barrier(0);
         if (j >= 12 && hs) {
           if (FIRST && ks == 0) acc[j] = (f32x16){0};
-        } else if (FIRST && ks == 0)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(opA(cs, j >> 2, j & 3), V[cs][j >> 1][j & 1],
-                                                       (f32x16){0}, 0, 0, 0);
-        else
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(opA(cs, j >> 2, j & 3), V[cs][j >> 1][j & 1],
-                                                       acc[j], 0, 0, 0);
+        } else {
+          mma(first_tag, ks, j);
+        }
         __builtin_amdgcn_sched_barrier(0);
         // the next k-step's operands, in the shadow of this one's MFMAs (its LDS reads were issued 6 MFMAs ago)
-        if (ks < 7 && j == W2_TX_AT) transform_x(ns);
-        if (ks < 7 && j == W2_TG_AT) transform_g(ns);
+        if ((ks < 7 || XF7) && j == W2_TX_AT) transform_x(ns);
+        if ((ks < 7 || XF7) && j == W2_TG_AT) transform_g(ns);
       }
-    }
-    edge_col = n_edge;
-    dma_wait();
-    __syncthreads();
-  };
-#ifndef W2_HALF_ROWS
-#define W2_HALF_ROWS 1  // A/B: 0 = every stage issues all 16 products (rounds 1 - 3)
+#if W2_STAGE_AHEAD
+      // products 12 - 15 (row 3 of G' g G'^T) behind ONE test per k-step; their two DMA slots go out ahead of it
+#if W2_DMA_KS == 2
+      if (ks < 2) { dma_unit(ks * 16 + 12); dma_unit(ks * 16 + 13); dma_unit(ks * 16 + 14); dma_unit(ks * 16 + 15); }
+#else
+      if (ks < 4) { dma_unit(ks * 8 + 6); dma_unit(ks * 8 + 7); }
 #endif
-  auto is_half = [&](int s) { return W2_HALF_ROWS && 2 * ((s / a.NTS) % a.TH) + 1 >= a.H; };
+      __builtin_amdgcn_sched_barrier(0);
+      if (!hs) {
+#pragma unroll
+        for (int j = 12; j < 16; ++j) {
+          mma(first_tag, ks, j);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else if (FIRST && ks == 0) {
+#pragma unroll
+        for (int j = 12; j < 16; ++j) acc[j] = (f32x16){0};
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#endif
+      W2_STAMP(T_KS + ks);
+#if W2_EARLY_SWAP
+      if (ks == 6) {
+        dma_wait();
+        W2_STAMP(T_WAIT);
+        __syncthreads();
+        W2_STAMP(T_BAR);
+      }
+#endif
+    }
+    edge_col = e_keep;
+    cur_half = h_keep;
+#if !W2_EARLY_SWAP
+    dma_wait();
+    W2_STAMP(T_WAIT);
+    __syncthreads();
+    W2_STAMP(T_BAR);
+#endif
+#if W2_TRACE
+    t_acc[T_NST] += 1;
+#endif
+  };
   if (s0 < s1) {
-    stage_body(std::true_type{}, is_half(s0), s0, 0);
+    stage_body(std::true_type{}, s0, 0);
     int cur = 1;
-    for (int s = s0 + 1; s < s1; ++s, cur ^= 1) stage_body(std::false_type{}, is_half(s), s, cur);
+    for (int s = s0 + 1; s < s1; ++s, cur ^= 1) stage_body(std::false_type{}, s, cur);
   } else {
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = (f32x16){0};
   }
+  W2_STAMP(T_HEAD);
 
   // Output transform R = A'^T (s s^T .* M) A', s = (1, 1/2, 1/2, 1), A'^T = [[1,1,1,0],[0,1,-1,0],
   // [0,1,1,-1]], on whole accumulators; partial[split][tap][co][ci]: lanes = consecutive ci.
@@ -849,6 +1091,15 @@ __global__ __launch_bounds__(256) void wino_wgrad_kernel(WinoWgArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+#if W2_TRACE
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // the stores have left
+  W2_STAMP(T_EPI);
+  if (a.trace != nullptr && tid == 0 && blockIdx.x < 4096) {
+#pragma unroll
+    for (int i = 0; i < 14; ++i) a.trace[blockIdx.x * 16 + i] = t_acc[i];
+  }
+#endif
+#undef W2_STAMP
 }
 
 int grid_for(size_t n) {
@@ -861,6 +1112,10 @@ int grid_for(size_t n) {
 
 static long long* g_wino_trace = nullptr;
 extern "C" void air_dbg_wino_trace(long long* p) { g_wino_trace = p; }
+#if W2_TRACE
+static long long* g_wino_wgrad_trace = nullptr;  // [16 x 4096], tools/wino_wgrad_kstep.py
+extern "C" void air_dbg_wino_wgrad_trace(long long* p) { g_wino_wgrad_trace = p; }
+#endif
 
 bool air_wino_ok(int B, int Kc, int H, int W, int M) {
   if (air_opt(AIR_OPT_NO_WINOGRAD) & 1) return false;
@@ -901,6 +1156,9 @@ int air_wino_wgrad_partials(const float* x, const float* dy, float* partial, int
   a.nseg = B * a.TH * a.NTS;
   a.ncob = Cout / 64; a.ncib = Cin / 64;
   a.nsplit = air_wino_wgrad_nsplit(B, Cin, H, W, Cout);
+#if W2_TRACE
+  a.trace = g_wino_wgrad_trace;
+#endif
   const size_t ldsb = 2 * WG_BUF * sizeof(float);
   static const bool attr_ok =
       hipFuncSetAttribute(reinterpret_cast<const void*>(wino_wgrad_kernel),

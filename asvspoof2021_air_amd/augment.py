@@ -47,6 +47,57 @@ def synthetic_ir_bank(n_device=27, n_space=3, taps=1024, sr=16000, seed=688):
     return torch.from_numpy(bank.astype(np.float32))
 
 
+MAX_BANK_TAPS = 65536  # air_ir_bank_convolve's limit per response
+
+
+class IRBank:
+    """Impulse responses of different lengths (device responses of a few milliseconds beside room responses of seconds),
+    for ``ir_convolve`` / ``ChannelAugment``: ``air_ir_bank_convolve`` charges each row of a batch for the response it
+    drew.  ``responses``: a sequence of 1-D arrays or tensors, each of 1 .. 65 536 taps (ValueError otherwise).
+    ``irs`` (n_ir, Hmax) float32, padded with zeros; ``taps`` (n_ir,) int32, the lengths - both move with ``to(device)``,
+    the kernel reads the tap counts on the device."""
+
+    def __init__(self, responses):
+        rows = [torch.as_tensor(np.asarray(r.detach().cpu() if torch.is_tensor(r) else r)).to(torch.float32) for r in responses]
+        if not rows:
+            raise ValueError("an IRBank needs at least one response")
+        for i, r in enumerate(rows):
+            if r.dim() != 1 or r.numel() < 1:
+                raise ValueError("response %d is empty or not 1-D: shape %s" % (i, tuple(r.shape)))
+            if r.numel() > MAX_BANK_TAPS:
+                raise ValueError("response %d has %d taps, above the limit of %d" % (i, r.numel(), MAX_BANK_TAPS))
+        self.taps = torch.tensor([r.numel() for r in rows], dtype=torch.int32)
+        self.irs = torch.zeros((len(rows), int(self.taps.max())), dtype=torch.float32)
+        for i, r in enumerate(rows):
+            self.irs[i, : r.numel()] = r
+
+    def __len__(self):
+        return self.irs.shape[0]
+
+    def to(self, device):
+        other = object.__new__(IRBank)
+        other.irs = self.irs.to(device=device, dtype=torch.float32).contiguous()
+        other.taps = self.taps.to(device=device, dtype=torch.int32).contiguous()
+        return other
+
+
+def synthetic_room_bank(n_device=27, n_space=3, sr=16000, seed=688, rt60=(0.2, 1.0)):
+    """``IRBank`` of ``n_device`` device responses - drawn as in ``synthetic_ir_bank``, 1024 taps - and ``n_space`` room
+    responses that run to their own -60 dB point: direct path + exponentially decaying noise of ``rt60 * sr`` taps, RT60
+    uniform in ``rt60`` seconds (3 200 .. 16 000 taps at 16 kHz).  Every response has unit energy."""
+    rows = list(synthetic_ir_bank(n_device, 0, 1024, sr, seed)) if n_device else []
+    rng = np.random.Generator(np.random.PCG64([seed, 1]))
+    for _ in range(n_space):
+        t60 = rng.uniform(rt60[0], rt60[1])
+        taps = min(max(int(round(t60 * sr)), 1), MAX_BANK_TAPS)
+        n = np.arange(taps)
+        h = 0.3 * rng.standard_normal(taps) * np.exp(-6.907755 * n / (t60 * sr))
+        h[: int(0.002 * sr)] *= 0.1
+        h[0] = 1.0
+        rows.append(torch.from_numpy((h / np.sqrt((h ** 2).sum())).astype(np.float32)))
+    return IRBank(rows)
+
+
 def _device_lengths(lengths, B, Lcap, device):
     """``lengths`` as the int32 (B,) device tensor the ragged kernel reads: a GPU tensor is used as is (the kernel clamps
     it to [1, Lcap]), a host tensor or sequence is checked (ValueError) and uploaded, as ``LFCC.forward_ragged`` does."""
@@ -69,7 +120,12 @@ def ir_convolve(pcm, irs, idx=None, normalize=True, out=None, lengths=None):
     ``lengths`` (B,) int32: a ragged batch in one launch (``air_ir_convolve_ragged``) - row b of ``pcm`` (B, Lcap), fp32
     or int16 (s / 32768), holds lengths[b] samples; what follows them is never read.  Row b of the fp32 result is, bit
     for bit, what the dense call gives for that utterance alone (convolved, truncated and peak-normalised over its own
-    samples), followed by zeros.  A GPU tensor is used as is, host values are checked (ValueError) and uploaded."""
+    samples), followed by zeros.  A GPU tensor is used as is, host values are checked (ValueError) and uploaded.
+
+    ``irs`` may be an ``IRBank`` (on the GPU): ``air_ir_bank_convolve``, dense or ragged, every row against the leading
+    ``taps`` columns of the response it drew - up to 65 536 of them."""
+    if isinstance(irs, IRBank):
+        return _bank_convolve(pcm, irs, idx, normalize, out, lengths)
     if not pcm.is_cuda or not irs.is_cuda:
         raise _hip.AirError("ir_convolve needs GPU tensors; there is no CPU fallback")
     B, L = pcm.shape
@@ -95,13 +151,39 @@ def ir_convolve(pcm, irs, idx=None, normalize=True, out=None, lengths=None):
     return y
 
 
+def _bank_convolve(pcm, bank, idx, normalize, out, lengths):
+    if not pcm.is_cuda or not bank.irs.is_cuda or not bank.taps.is_cuda:
+        raise _hip.AirError("ir_convolve needs GPU tensors; there is no CPU fallback")
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
+    B, L = pcm.shape
+    n_ir, H = bank.irs.shape
+    if lengths is not None:
+        lengths = _device_lengths(lengths, B, L, pcm.device)
+    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
+    lib = _hip.lib()
+    n = lib.air_ir_bank_ws_bytes(_hip.ci(B), _hip.ci(L), _hip.ci(n_ir), _hip.ci(H))
+    ws = ops.workspace(n, pcm.device)
+    i16 = pcm.dtype == torch.int16
+    null = _hip.dptr(None, allow_none=True)
+    _hip.check(lib.air_ir_bank_convolve(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
+                                        _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True), _hip.dptr(bank.irs),
+                                        _hip.ci(n_ir), _hip.ci(H), _hip.dptr(bank.taps, torch.int32),
+                                        _hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0), _hip.dptr(y),
+                                        _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream()), "air_ir_bank_convolve")
+    return y
+
+
 class ChannelAugment:
-    """Per-utterance random IR from a bank, applied with probability ``p``."""
+    """Per-utterance random IR from a bank - a (n_ir, H) tensor or an ``IRBank`` - applied with probability ``p``."""
 
     supports_lengths = True  # __call__(pcm, lengths=...) augments a ragged batch over each row's own samples (Trainer.step)
 
     def __init__(self, irs=None, p=1.0, seed=688, normalize=True, device="cuda"):
-        self.irs = (irs if irs is not None else synthetic_ir_bank()).to(device=device, dtype=torch.float32).contiguous()
+        if isinstance(irs, IRBank):
+            self.irs = irs.to(device)
+        else:
+            self.irs = (irs if irs is not None else synthetic_ir_bank()).to(device=device, dtype=torch.float32).contiguous()
         self.p = float(p)
         self.normalize = normalize
         self.rng = np.random.Generator(np.random.PCG64(seed))
@@ -109,7 +191,7 @@ class ChannelAugment:
 
     def draw(self, batch):
         """(B,) int32 IR indices, -1 = leave the utterance unchanged."""
-        idx = self.rng.integers(0, self.irs.shape[0], size=batch).astype(np.int32)
+        idx = self.rng.integers(0, len(self.irs), size=batch).astype(np.int32)
         if self.p < 1.0:
             idx[self.rng.random(batch) >= self.p] = -1
         return idx

@@ -34,6 +34,11 @@
 // y[b, :L_b] carries the bits of the dense call on that utterance alone.  [L_b, Lcap) is written as zero; a workgroup
 // whose outputs all lie there stores its zeros and returns.  The dense entry point launches the fp32 instantiation
 // without lengths (L_b = Lcap = L).
+//
+// Banks of responses of different lengths, up to 65 536 taps (air_ir_bank_convolve): rows that drew at most 1025 taps run
+// the overlap-save form above, longer ones its uniformly partitioned extension - 4096-point transforms, partitions and
+// hop of 2048 samples, the products accumulated in the frequency domain and one inverse per pair of output blocks.  The
+// geometry is described in front of those kernels, at the end of the anonymous namespace.
 #include "air_common.h"
 #include "air_fft16.h"
 #include "air_options.h"
@@ -256,23 +261,14 @@ __global__ __launch_bounds__(FC_NT) void fc_spectrum_kernel(const float* __restr
   for (int k = 0; k < 16; ++k) o[k] = v[k] * (1.0f / (float)FC_N);
 }
 
-// blockIdx.x = pair of output blocks (2 p, 2 p + 1) of utterance blockIdx.y
+// The pair of output blocks (2 p, 2 p + 1), p = pair, of one utterance (baseA = 2 p FC_V < L) against ONE spectrum hs (the
+// response's, at this thread's 16 elements): shared by fc_convolve_kernel and, for the rows of a bank that drew a response
+// of at most FC_MAXH taps, by pb_convolve_kernel - the same statements, so those rows carry the same bits.
 template <typename T>
-__global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
-                                                            const cf* __restrict__ spec, const cf* __restrict__ tw,
-                                                            const int* __restrict__ idx, float* __restrict__ y,
-                                                            unsigned* __restrict__ peaks, int n_ir) {
-  __shared__ cf buf[FC_LDS];
-  const int b = blockIdx.y, t = threadIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap);
-  const T* __restrict__ xb = x + (size_t)b * Lcap;
-  float* __restrict__ yb = y + (size_t)b * Lcap;
-  const int baseA = 2 * blockIdx.x * FC_V, baseB = baseA + FC_V;  // first output sample of either block
-  const int ir = idx ? min(idx[b], n_ir - 1) : 0;
-  if (ir < 0 || baseA >= L) {  // pass-through utterance, or a pair wholly behind the row's length: zeros
-    ir_copy_span(xb, yb, baseA, 2 * FC_V, L, Lcap, t, FC_NT);
-    return;
-  }
+__device__ __forceinline__ void fc_convolve_pair(const T* __restrict__ xb, float* __restrict__ yb, int L, int Lcap, int pair,
+                                                 const cf* __restrict__ hs, const cf* __restrict__ tw, cf* __restrict__ buf,
+                                                 unsigned* __restrict__ peaks, int b, int t) {
+  const int baseA = 2 * pair * FC_V, baseB = baseA + FC_V;  // first output sample of either block
   cf v[16];
   float xpeak = 0.0f;
 #pragma unroll
@@ -284,7 +280,6 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict_
     if (j >= FC_OV / 256) xpeak = fmaxf(xpeak, fmaxf(fabsf(a), fabsf(c)));  // the blocks' own samples
   }
   fc_forward(v, buf, tw, t);
-  const cf* __restrict__ hs = spec + (size_t)ir * FC_N + 16 * t;
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] = cmul(v[k], hs[k]);
   fc_inverse(v, buf, tw, t);
@@ -313,6 +308,25 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict_
       atomic_max_pos(peaks + 2 * b + 1, ypeak);
     }
   }
+}
+
+// blockIdx.x = pair of output blocks (2 p, 2 p + 1) of utterance blockIdx.y
+template <typename T>
+__global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                            const cf* __restrict__ spec, const cf* __restrict__ tw,
+                                                            const int* __restrict__ idx, float* __restrict__ y,
+                                                            unsigned* __restrict__ peaks, int n_ir) {
+  __shared__ cf buf[FC_LDS];
+  const int b = blockIdx.y, t = threadIdx.x;
+  const int L = ir_row_len(lengths, b, Lcap);
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
+  const int ir = idx ? min(idx[b], n_ir - 1) : 0;
+  if (ir < 0 || 2 * (int)blockIdx.x * FC_V >= L) {  // pass-through utterance, or a pair wholly behind the row's length: zeros
+    ir_copy_span(xb, yb, 2 * (int)blockIdx.x * FC_V, 2 * FC_V, L, Lcap, t, FC_NT);
+    return;
+  }
+  fc_convolve_pair(xb, yb, L, Lcap, (int)blockIdx.x, spec + (size_t)ir * FC_N + 16 * t, tw, buf, peaks, b, t);
 }
 
 inline size_t fc_align(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -581,6 +595,205 @@ int g711_launch(const T* x, int B, int Lcap, const int* lengths, const float* fi
   return AIR_OK;
 }
 
+// ---- bank of responses of different lengths (air_ir_bank_convolve) ---------------------------------------------------
+// Row b draws response i = idx[b] of taps_i = clamp(ir_taps[i], 1, Hmax) taps (device data).  Two forms in one launch:
+//   * taps_i <= FC_MAXH: fc_convolve_pair against the spectrum of the response's first partition - the statements, the
+//     block geometry (two 3072-sample blocks per transform) and hence the bits of air_ir_convolve_ragged;
+//   * longer: UNIFORMLY PARTITIONED overlap-save.  Geometry: transform N = 4096, partition length = hop = PB_P = 2048
+//     (taps - 1 + hop = 4095 <= N), so the response is cut into ceil(taps_i / 2048) partitions h_p and output block k
+//     (samples [2048 k, 2048 k + 2048)) is the last 2048 samples of IFFT(sum_p X_{k-p} H_p), X_s the transform of
+//     "segment" s = samples [2048 (s - 1), 2048 (s + 1)).  Two real segments ride one complex transform as before; a
+//     product with a (real response's) spectrum keeps them apart, so a packed spectrum serves every partition that needs
+//     BOTH its segments: output blocks (2 j, 2 j + 1) take, for even p, the "even" packing Ze_m = (segment 2 m, 2 m + 1)
+//     at m = j - p / 2 and, for odd p, the "odd" packing Zo_m = (segment 2 m - 1, 2 m) at m = j - (p - 1) / 2.
+//     pb_forward_kernel transforms every packing of a long row ONCE into the workspace (the odd ones only for rows with
+//     a second partition); pb_convolve_kernel accumulates Z H over the row's own partitions in ascending p in registers
+//     (16 complex values per thread, as the transforms) and takes ONE inverse per pair of output blocks.  Which segments
+//     share a transform depends on the sample index alone, and the sum runs over the row's own partitions, so the bits of
+//     y[b, :L_b] do not depend on Lcap, B or the other rows.
+// Spectra of both forms keep fc_forward's digit-reversed order; the tables (twiddles, partition spectra) are rebuilt per
+// call, as in ir_launch.  Grids are sized by the host-known Lcap and Hmax; workgroups of partitions a response does not
+// have, of packings a row does not need and of blocks behind L_b return at once (the last kind after writing zeros).
+constexpr int PB_P = 2048;                 // partition length = hop of the long form
+constexpr int PB_MAXH = 65536;             // 32 partitions
+static_assert(2 * PB_P == FC_N && PB_P % 256 == 0, "partition + hop fill the transform");
+
+__device__ __forceinline__ int pb_taps(const int* __restrict__ ir_taps, int ir, int Hmax) { return min(max(ir_taps[ir], 1), Hmax); }
+
+// blockIdx.x = partition, blockIdx.y = response.  spec[(i * nparts + p) * FC_N ...] = FFT(h_i[2048 p, 2048 p + 2048) & 0) / 4096
+__global__ __launch_bounds__(FC_NT) void pb_spectrum_kernel(const float* __restrict__ irs, int Hmax, const int* __restrict__ ir_taps,
+                                                            const cf* __restrict__ tw, cf* __restrict__ spec, int nparts) {
+  __shared__ cf buf[FC_LDS];
+  const int t = threadIdx.x, i = blockIdx.y, p = blockIdx.x;
+  const int taps = pb_taps(ir_taps, i, Hmax);
+  if (p * PB_P >= taps) return;  // a partition this response does not have: never read
+  const float* __restrict__ h = irs + (size_t)i * Hmax;
+  cf v[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int n = p * PB_P + 256 * j + t;
+    v[j] = cf{(j < PB_P / 256 && n < taps) ? h[n] : 0.0f, 0.0f};
+  }
+  fc_forward(v, buf, tw, t);
+  cf* __restrict__ o = spec + ((size_t)i * nparts + p) * FC_N + 16 * t;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) o[k] = v[k] * (1.0f / (float)FC_N);
+}
+
+// blockIdx.x = m, blockIdx.y = packing (0: Ze_m, 1: Zo_m), blockIdx.z = row.  zs[((b * nz + packing) * npair + m) * FC_N ...]
+template <typename T>
+__global__ __launch_bounds__(FC_NT) void pb_forward_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                           int Hmax, const int* __restrict__ ir_taps, const cf* __restrict__ tw,
+                                                           const int* __restrict__ idx, cf* __restrict__ zs,
+                                                           unsigned* __restrict__ peaks, int n_ir, int npair) {
+  __shared__ cf buf[FC_LDS];
+  const int t = threadIdx.x, m = blockIdx.x, odd = blockIdx.y, b = blockIdx.z;
+  const int ir = idx ? min(idx[b], n_ir - 1) : 0;
+  if (ir < 0) return;
+  const int taps = pb_taps(ir_taps, ir, Hmax);
+  if (taps <= FC_MAXH || (odd && taps <= PB_P)) return;  // the short form; a row without an odd partition
+  const int L = ir_row_len(lengths, b, Lcap);
+  if (2 * m * PB_P >= L) return;  // no pair of output blocks of this row reaches back to m
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  const int s0 = (2 * m - odd - 1) * PB_P;  // first sample of the real part's segment; the imaginary part's is PB_P further
+  cf v[16];
+  float xpeak = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int mA = s0 + 256 * j + t, mB = mA + PB_P;
+    const float a = (mA >= 0 && mA < L) ? ir_sample(xb, mA) : 0.0f;
+    const float c = (mB >= 0 && mB < L) ? ir_sample(xb, mB) : 0.0f;
+    v[j] = cf{a, c};
+    if (j >= PB_P / 256) xpeak = fmaxf(xpeak, fmaxf(fabsf(a), fabsf(c)));  // (even packing) blocks 2 m and 2 m + 1: every sample once
+  }
+  fc_forward(v, buf, tw, t);
+  cf* __restrict__ o = zs + (((size_t)b * gridDim.y + odd) * npair + m) * FC_N + 16 * t;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) o[k] = v[k];
+  if (peaks && !odd) {
+    xpeak = air_wave_max(xpeak);
+    if ((t & 63) == 0) atomic_max_pos(peaks + 2 * b, xpeak);
+  }
+}
+
+// blockIdx.x = pair of output blocks of utterance blockIdx.y: 3072-sample blocks for a short response, 2048 for a long one
+template <typename T>
+__global__ __launch_bounds__(FC_NT) void pb_convolve_kernel(const T* __restrict__ x, int Lcap, const int* __restrict__ lengths,
+                                                            int Hmax, const int* __restrict__ ir_taps, const cf* __restrict__ spec,
+                                                            const cf* __restrict__ zs, const cf* __restrict__ tw,
+                                                            const int* __restrict__ idx, float* __restrict__ y,
+                                                            unsigned* __restrict__ peaks, int n_ir, int nparts, int nz, int npair) {
+  __shared__ cf buf[FC_LDS];
+  const int b = blockIdx.y, t = threadIdx.x, j = blockIdx.x;
+  const int L = ir_row_len(lengths, b, Lcap);
+  const T* __restrict__ xb = x + (size_t)b * Lcap;
+  float* __restrict__ yb = y + (size_t)b * Lcap;
+  const int ir = idx ? min(idx[b], n_ir - 1) : 0;
+  const int taps = ir < 0 ? 1 : pb_taps(ir_taps, ir, Hmax);
+  if (taps <= FC_MAXH) {  // pass-through and short rows: fc_convolve_kernel's tiling (spans past Lcap store nothing)
+    if (ir < 0 || 2 * j * FC_V >= L)
+      ir_copy_span(xb, yb, 2 * j * FC_V, 2 * FC_V, L, Lcap, t, FC_NT);
+    else
+      fc_convolve_pair(xb, yb, L, Lcap, j, spec + (size_t)ir * nparts * FC_N + 16 * t, tw, buf, peaks, b, t);
+    return;
+  }
+  const int base = 2 * j * PB_P;
+  if (base >= L) {  // a pair wholly behind the row's length: zeros
+    ir_copy_span(xb, yb, base, 2 * PB_P, L, Lcap, t, FC_NT);
+    return;
+  }
+  const int np = (taps + PB_P - 1) / PB_P;
+  const cf* __restrict__ hrow = spec + (size_t)ir * nparts * FC_N + 16 * t;
+  const cf* __restrict__ zrow = zs + (size_t)b * nz * npair * FC_N + 16 * t;
+  cf v[16];
+  {
+    const cf* __restrict__ z = zrow + (size_t)j * FC_N;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = cmul(z[k], hrow[k]);
+  }
+  for (int p = 1; p < np; ++p) {
+    const int m = j - (p >> 1);
+    if (m < 0) break;  // segments in front of the utterance: zero
+    const cf* __restrict__ z = zrow + ((size_t)(p & 1) * npair + m) * FC_N;
+    const cf* __restrict__ h = hrow + (size_t)p * FC_N;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = v[k] + cmul(z[k], h[k]);
+  }
+  fc_inverse(v, buf, tw, t);
+  float ypeak = 0.0f;
+#pragma unroll
+  for (int a = PB_P / 256; a < 16; ++a) {  // behind the history: block 2 j in the real, block 2 j + 1 in the imaginary part
+    const int nA = base + 256 * a + t - PB_P, nB = nA + PB_P;
+    if (nA < L) {
+      yb[nA] = v[a][0];
+      ypeak = fmaxf(ypeak, fabsf(v[a][0]));
+    } else if (nA < Lcap) {
+      yb[nA] = 0.0f;
+    }
+    if (nB < L) {
+      yb[nB] = v[a][1];
+      ypeak = fmaxf(ypeak, fabsf(v[a][1]));
+    } else if (nB < Lcap) {
+      yb[nB] = 0.0f;
+    }
+  }
+  if (peaks) {
+    ypeak = air_wave_max(ypeak);
+    if ((t & 63) == 0) atomic_max_pos(peaks + 2 * b + 1, ypeak);
+  }
+}
+
+struct PbPlan {  // host-known geometry of one call
+  int nparts, nz, npair, gx;
+  size_t off_tw, off_spec, off_z, total;
+};
+
+inline PbPlan pb_plan(int B, int Lcap, int n_ir, int Hmax) {
+  PbPlan g;
+  g.nparts = (Hmax + PB_P - 1) / PB_P;
+  g.nz = Hmax <= FC_MAXH ? 0 : (g.nparts > 1 ? 2 : 1);  // packings kept per row: none, even, even + odd
+  g.npair = ((Lcap + PB_P - 1) / PB_P + 1) / 2;
+  const int short_pairs = ((Lcap + FC_V - 1) / FC_V + 1) / 2;
+  g.gx = g.nz ? (g.npair > short_pairs ? g.npair : short_pairs) : short_pairs;
+  g.off_tw = fc_align(air_ir_convolve_ws_bytes(B));
+  g.off_spec = g.off_tw + fc_align((size_t)FC_N * sizeof(cf));
+  g.off_z = g.off_spec + (size_t)n_ir * g.nparts * FC_N * sizeof(cf);
+  g.total = g.off_z + (size_t)B * g.nz * g.npair * FC_N * sizeof(cf);
+  return g;
+}
+
+template <typename T>
+int pb_launch(const T* x, int B, int Lcap, const int* lengths, const float* irs, int n_ir, int Hmax, const int* ir_taps,
+              const int* ir_idx, int normalize, float* y, void* ws, hipStream_t st) {
+  const PbPlan g = pb_plan(B, Lcap, n_ir, Hmax);
+  char* base = reinterpret_cast<char*>(ws);
+  unsigned* peaks = normalize ? reinterpret_cast<unsigned*>(ws) : nullptr;
+  cf* tw = reinterpret_cast<cf*>(base + g.off_tw);
+  cf* spec = reinterpret_cast<cf*>(base + g.off_spec);
+  cf* zs = reinterpret_cast<cf*>(base + g.off_z);
+  if (peaks) {  // (a kernel, not a memset: see g711_launch)
+    hipLaunchKernelGGL(g711_clear_peaks_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, st, peaks, 2 * B);
+    AIR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(fc_twiddle_kernel, dim3(FC_N / 256), dim3(256), 0, st, tw);
+  AIR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pb_spectrum_kernel, dim3(g.nparts, n_ir), dim3(FC_NT), 0, st, irs, Hmax, ir_taps, tw, spec, g.nparts);
+  AIR_CHECK_LAUNCH();
+  if (g.nz) {
+    hipLaunchKernelGGL(pb_forward_kernel<T>, dim3(g.npair, g.nz, B), dim3(FC_NT), 0, st, x, Lcap, lengths, Hmax, ir_taps, tw,
+                       ir_idx, zs, peaks, n_ir, g.npair);
+    AIR_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(pb_convolve_kernel<T>, dim3(g.gx, B), dim3(FC_NT), 0, st, x, Lcap, lengths, Hmax, ir_taps, spec, zs, tw,
+                     ir_idx, y, peaks, n_ir, g.nparts, g.nz, g.npair);
+  AIR_CHECK_LAUNCH();
+  if (normalize) {
+    hipLaunchKernelGGL(fir_rescale_kernel, dim3(16, B), dim3(256), 0, st, y, Lcap, lengths, ir_idx, peaks);
+    AIR_CHECK_LAUNCH();
+  }
+  return AIR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,6 +841,25 @@ int air_g711_ragged(const float* x, const int16_t* x16, int B, int Lcap, const i
     return g711_launch(reinterpret_cast<const short*>(x16), B, Lcap, lengths_dev_or_null, fir, ntaps, law_idx, resample,
                        normalize, y, codes_or_null, ws, st);
   return g711_launch(x, B, Lcap, lengths_dev_or_null, fir, ntaps, law_idx, resample, normalize, y, codes_or_null, ws, st);
+}
+
+size_t air_ir_bank_ws_bytes(int B, int Lcap, int n_ir, int Hmax) {
+  if (B <= 0 || Lcap <= 0 || n_ir <= 0 || Hmax <= 0 || Hmax > PB_MAXH) return 0;
+  return pb_plan(B, Lcap, n_ir, Hmax).total;
+}
+
+int air_ir_bank_convolve(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev_or_null, const float* irs,
+                         int n_ir, int Hmax, const int* ir_taps_dev, const int* ir_idx, int normalize, float* y, void* ws,
+                         size_t ws_bytes, air_stream_t stream) {
+  if ((x != nullptr) == (x16 != nullptr) || !y || !irs || !ir_taps_dev || B <= 0 || B > 65535 || Lcap <= 0 || n_ir <= 0 ||
+      n_ir > 65535 || Hmax <= 0 || Hmax > PB_MAXH || (x && x == y))
+    return AIR_EINVAL;
+  if (!ws || ws_bytes < air_ir_bank_ws_bytes(B, Lcap, n_ir, Hmax)) return AIR_EWORKSPACE;
+  hipStream_t st = air_stream(stream);
+  if (x16)
+    return pb_launch(reinterpret_cast<const short*>(x16), B, Lcap, lengths_dev_or_null, irs, n_ir, Hmax, ir_taps_dev, ir_idx,
+                     normalize, y, ws, st);
+  return pb_launch(x, B, Lcap, lengths_dev_or_null, irs, n_ir, Hmax, ir_taps_dev, ir_idx, normalize, y, ws, st);
 }
 
 }  // extern "C"

@@ -310,6 +310,33 @@ int air_ir_convolve(const float* x, int B, int L, const float* irs, int n_ir, in
 int air_ir_convolve_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev,
                            const float* irs, int n_ir, int H, const int* ir_idx, int normalize,
                            float* y, void* ws, size_t ws_bytes, air_stream_t stream);
+/* A BANK of responses of different lengths, each up to 65 536 taps (room responses: tenths of a second to seconds), on a
+ * dense or ragged batch.  Rows, lengths (a NULL pointer: the dense batch, L_b = Lcap), the x / x16 choice, ir_idx[b] < 0,
+ * the zero tail y[b, L_b:], normalize and the two peaks per row at the head of the workspace are exactly as in
+ * air_ir_convolve_ragged.  irs is (n_ir, Hmax) fp32; ir_taps_dev[i] is DEVICE data, clamped by the kernels into
+ * [1, Hmax]: the leading taps_i columns of row i are the response, columns at or behind it are never read (they may hold
+ * anything).  y[b, :L_b] = (x_b * irs[i, :taps_i])[:L_b], i = ir_idx[b]; each row pays for its own response only:
+ *   taps_i <= 1025: the overlap-save form of air_ir_convolve_ragged (two 3072-sample blocks per 4096-point transform) -
+ *     the same device code, so the row carries, bit for bit, what that call gives with the bank's first 1025 columns
+ *     zeroed behind taps_i;
+ *   taps_i > 1025: uniformly partitioned overlap-save - 4096-point transforms, the response cut into partitions of 2048
+ *     taps, the hop 2048 samples; every pair of input segments is transformed once into the workspace, an output pair
+ *     accumulates (segment spectrum x partition spectrum) over the row's own ceil(taps_i / 2048) partitions in registers
+ *     and takes one inverse transform.
+ * Nothing depends on Lcap, B or the other rows: y[b, :L_b] carries the bits of the call on that utterance alone.
+ * Lengths, indices and tap counts are device data and nothing synchronises with the host, so the call can be captured in
+ * a graph and replayed after they are rewritten; the peaks are cleared by a kernel; the twiddle and partition-spectra
+ * tables are rebuilt per call, so the bank may be rewritten in place between calls.  Launches: [clear peaks,] twiddles,
+ * partition spectra (ceil(Hmax / 2048) x n_ir workgroups), segment spectra (only with Hmax > 1025), convolve [, rescale];
+ * the grids are sized by Lcap and Hmax, workgroups of partitions a response does not have, of rows on the other form and
+ * of blocks behind L_b return at once.  Workspace: air_ir_bank_ws_bytes (peaks + tables + with Hmax > 1025 the segment
+ * spectra, B x 2 x ceil(Lcap / 4096) x 32 KB); 0 for arguments the call refuses.  Hmax > 65536, a NULL ir_taps_dev, irs
+ * or y, both or neither of x / x16, x == y, a non-positive size (or B, n_ir above 65535): AIR_EINVAL, ahead of any HIP
+ * call; a workspace below air_ir_bank_ws_bytes: AIR_EWORKSPACE. */
+size_t air_ir_bank_ws_bytes(int B, int Lcap, int n_ir, int Hmax);
+int air_ir_bank_convolve(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev_or_null,
+                         const float* irs, int n_ir, int Hmax, const int* ir_taps_dev, const int* ir_idx,
+                         int normalize, float* y, void* ws, size_t ws_bytes, air_stream_t stream);
 
 /* G.711 transmission codec ahead of the IR convolution - the first half of channel_simulation/simulated_device_channel.py:
  * 47-54 (codec, then device), for the two sample-parallel entries of the reference's codec list, G.711 mu-law and A-law

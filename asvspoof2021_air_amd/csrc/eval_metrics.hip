@@ -1,0 +1,405 @@
+// Exact DET-curve minima on the device: EER point and min t-DCF point of up to 2^20 trials (air_hip.h, "evaluation
+// metrics").  Replaces the sort + cumsum + argmin of eval_metrics.py:19-46 and the argmin over compute_tDCF's curve
+// (eval_metrics.py:157-172, evaluate_tDCF_asvspoof19.py:58-59).
+//
+// One 64-bit key per trial: ((order-preserving image of the fp32 score) << 1) | is_spoof.  The reference's stable
+// mergesort of [bona fide..., spoof...] orders trials by score with bona fide first among equal scores; only the
+// cumulative class counts at each curve point matter, and equal keys are interchangeable, so ANY correct sort of
+// the keys gives the reference's curve.  -0.0 is canonicalised to +0.0 (numpy compares them equal), NaN is counted
+// and refused by the caller.  Integers up to the two fp64 divisions per point, which are correctly rounded on both
+// sides (the build has -ffp-contract=off): results are bit-equal to the host code or an error.
+//
+// Sort: bitonic network over npad = max(EV_BLOCK, next power of two >= n) keys, padded with all-ones sentinels (above
+// every real key: real keys stay below 2^33).  Sub-sequences of EV_BLOCK keys are sorted / merged in LDS, the strides
+// >= EV_BLOCK run in global memory, one launch per stride.  EV_BLOCK * 8 B = 32 KiB per workgroup: five workgroups fit
+// the 160 KiB of a CU, the 8 waves of each keep four resident under the 32-wave cap.
+#include "air_common.h"
+
+#define EV_BLOCK 4096
+#define EV_THREADS 512
+#define EV_PER_THREAD (EV_BLOCK / EV_THREADS)
+#define EV_MAX_N (1 << 20)
+#define EV_MAX_BLOCKS (EV_MAX_N / EV_BLOCK)
+
+static_assert(sizeof(air_eval_record) == 64, "air_eval_record is 64 bytes");
+
+namespace {
+
+struct EvBest {  // 16 bytes: one candidate of the lexicographic (value, index) minimum
+  double v;
+  uint32_t k;   // curve point: the k lowest trials rejected
+  uint32_t rn;  // spoof trials among them
+};
+
+__device__ __forceinline__ float ev_key_score(uint64_t key) {
+  const uint32_t o = (uint32_t)(key >> 1);
+  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+__device__ __forceinline__ bool ev_better(const EvBest& a, const EvBest& b) {
+  return a.v < b.v || (a.v == b.v && a.k < b.k);
+}
+
+__device__ __forceinline__ EvBest ev_wave_best(EvBest b) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    EvBest c;
+    c.v = __shfl_xor(b.v, o, 64);
+    c.k = __shfl_xor(b.k, o, 64);
+    c.rn = __shfl_xor(b.rn, o, 64);
+    if (ev_better(c, b)) b = c;
+  }
+  return b;
+}
+
+__device__ __forceinline__ uint32_t ev_wave_sum_u(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// keys[i] for i < npad (a multiple of the 1024 keys of a workgroup); class and NaN / inf counts into rec (zeroed by the
+// caller on the same stream; integer atomics: the totals do not depend on their order)
+template <typename L>
+__global__ __launch_bounds__(256) void ev_keys_kernel(const float* __restrict__ scores, const L* __restrict__ labels,
+                                                       int n, int npad, int negate, uint64_t* __restrict__ keys,
+                                                       air_eval_record* rec) {
+  uint32_t n_tar = 0, n_non = 0, n_nan = 0, n_inf = 0;
+  const int base = blockIdx.x * (256 * 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int i = base + e * 256 + threadIdx.x;
+    uint64_t key = ~0ull;
+    if (i < n) {
+      uint32_t u = __float_as_uint(scores[i]);
+      if (negate) u ^= 0x80000000u;
+      const uint32_t mag = u & 0x7fffffffu;
+      if (mag == 0u) u = 0u;  // -0.0 -> +0.0
+      n_nan += mag > 0x7f800000u;
+      n_inf += mag == 0x7f800000u;
+      const uint32_t spoof = labels[i] != 0;
+      n_non += spoof;
+      n_tar += spoof ^ 1u;
+      const uint32_t o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+      key = ((uint64_t)o << 1) | spoof;
+    }
+    keys[i] = key;
+  }
+  n_tar = ev_wave_sum_u(n_tar);
+  n_non = ev_wave_sum_u(n_non);
+  n_nan = ev_wave_sum_u(n_nan);
+  n_inf = ev_wave_sum_u(n_inf);
+  if ((threadIdx.x & 63) == 0) {
+    if (n_tar) atomicAdd(&rec->n_tar, n_tar);
+    if (n_non) atomicAdd(&rec->n_non, n_non);
+    if (n_nan) atomicAdd(&rec->n_nan, n_nan);
+    if (n_inf) atomicAdd(&rec->n_inf, n_inf);
+  }
+}
+
+__device__ __forceinline__ void ev_cmpx(uint64_t* s, int i, int j, bool asc) {
+  const uint64_t a = s[i], b = s[i | j];
+  if ((a > b) == asc) {
+    s[i] = b;
+    s[i | j] = a;
+  }
+}
+
+// the steps j < EV_BLOCK of the stages k = kfirst .. klast of the network, on the EV_BLOCK keys of this workgroup:
+// sort (kfirst = 2, klast = EV_BLOCK, every stage from its own j = k / 2) or the tail of one global stage
+// (kfirst = klast = k > EV_BLOCK, j from EV_BLOCK / 2)
+__global__ __launch_bounds__(EV_THREADS) void ev_sort_block_kernel(uint64_t* __restrict__ keys, int kfirst, int klast) {
+  __shared__ uint64_t s[EV_BLOCK];
+  const size_t base = (size_t)blockIdx.x * EV_BLOCK;
+  for (int i = threadIdx.x; i < EV_BLOCK; i += EV_THREADS) s[i] = keys[base + i];
+  __syncthreads();
+  for (int k = kfirst; k <= klast; k <<= 1) {
+    const int j0 = k > EV_BLOCK ? EV_BLOCK / 2 : k / 2;
+    for (int j = j0; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < EV_BLOCK / 2; t += EV_THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        ev_cmpx(s, i, j, ((base + i) & (size_t)k) == 0);
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < EV_BLOCK; i += EV_THREADS) keys[base + i] = s[i];
+}
+
+// one step (stride j >= EV_BLOCK) of stage k over npad keys, one pair per thread
+__global__ __launch_bounds__(256) void ev_merge_global_kernel(uint64_t* __restrict__ keys, int npad, int j, int k) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= npad / 2) return;
+  const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+  const uint64_t a = keys[i], b = keys[i | j];
+  if ((a > b) == ((i & k) == 0)) {
+    keys[i] = b;
+    keys[i | j] = a;
+  }
+}
+
+// spoof trials in each EV_BLOCK of the sorted keys
+__global__ __launch_bounds__(256) void ev_counts_kernel(const uint64_t* __restrict__ keys, int n, uint32_t* __restrict__ blockcnt,
+                                                         air_eval_record* rec) {
+  __shared__ uint32_t part[4];
+  const int base = blockIdx.x * EV_BLOCK;
+  uint32_t c = 0;
+  for (int i = threadIdx.x; i < EV_BLOCK; i += 256)
+    if (base + i < n) c += (uint32_t)(keys[base + i] & 1ull);
+  c = ev_wave_sum_u(c);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    blockcnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    if (blockIdx.x == 0) rec->n_distinct = 0;  // (ev_curve_kernel counts into it)
+  }
+}
+
+// per EV_BLOCK of curve points: inclusive scan of the class bit, both error rates in fp64, the block's first minimum
+// of |frr - far| and of the normalised t-DCF
+__global__ __launch_bounds__(EV_THREADS) void ev_curve_kernel(const uint64_t* __restrict__ keys, int n,
+                                                               const uint32_t* __restrict__ blockcnt, int want_dcf, double c1,
+                                                               double c2, air_eval_record* rec, EvBest* __restrict__ partial) {
+  __shared__ uint32_t wave_tot[EV_THREADS / 64];
+  __shared__ uint32_t base_s;
+  __shared__ EvBest best_s[2][EV_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // spoof trials below this block
+  if (wave == 0) {
+    uint32_t b = 0;
+    for (int q = lane; q < (int)blockIdx.x; q += 64) b += blockcnt[q];
+    b = ev_wave_sum_u(b);
+    if (lane == 0) base_s = b;
+  }
+  const int first = blockIdx.x * EV_BLOCK + tid * EV_PER_THREAD;
+  uint64_t key[EV_PER_THREAD];
+  uint32_t mine = 0, distinct = 0;
+  uint64_t prev = (first > 0 && first < n) ? keys[first - 1] : 0;
+#pragma unroll
+  for (int e = 0; e < EV_PER_THREAD; ++e) {
+    const int i = first + e;
+    key[e] = i < n ? keys[i] : ~0ull;
+    if (i < n) {
+      mine += (uint32_t)(key[e] & 1ull);
+      distinct += (i == 0) || ((key[e] >> 1) != (prev >> 1));
+      prev = key[e];
+    }
+  }
+  // exclusive scan of the threads' counts: inside the wave, then over the waves
+  uint32_t incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  uint32_t rn = base_s + incl - mine;
+  for (int w = 0; w < wave; ++w) rn += wave_tot[w];
+
+  const double n_tar = (double)rec->n_tar, n_non = (double)rec->n_non;
+  const uint32_t n_non_u = rec->n_non;
+  const double cmin = c1 < c2 ? c1 : c2;
+  EvBest eer, dcf;
+  eer.v = dcf.v = __longlong_as_double(0x7ff0000000000000ll);
+  eer.k = dcf.k = 0xffffffffu;
+  eer.rn = dcf.rn = 0;
+  if (first == 0) {  // curve point 0: nothing rejected, FRR 0, FAR 1
+    const double frr = 0.0 / n_tar, far = (double)n_non_u / n_non;
+    eer.v = fabs(frr - far);
+    dcf.v = (c1 * frr + c2 * far) / cmin;
+    eer.k = dcf.k = 0;
+  }
+#pragma unroll
+  for (int e = 0; e < EV_PER_THREAD; ++e) {
+    const int i = first + e;
+    if (i < n) {
+      rn += (uint32_t)(key[e] & 1ull);
+      const uint32_t k = (uint32_t)i + 1u;
+      const double frr = (double)(k - rn) / n_tar;
+      const double far = (double)(n_non_u - rn) / n_non;
+      const double d = fabs(frr - far);
+      if (d < eer.v) {
+        eer.v = d;
+        eer.k = k;
+        eer.rn = rn;
+      }
+      if (want_dcf) {
+        const double t = (c1 * frr + c2 * far) / cmin;
+        if (t < dcf.v) {
+          dcf.v = t;
+          dcf.k = k;
+          dcf.rn = rn;
+        }
+      }
+    }
+  }
+  eer = ev_wave_best(eer);
+  dcf = ev_wave_best(dcf);
+  distinct = ev_wave_sum_u(distinct);
+  if (lane == 0) {
+    best_s[0][wave] = eer;
+    best_s[1][wave] = dcf;
+    if (distinct) atomicAdd(&rec->n_distinct, distinct);
+  }
+  __syncthreads();
+  if (tid < 2) {
+    EvBest b = best_s[tid][0];
+    for (int w = 1; w < EV_THREADS / 64; ++w)
+      if (ev_better(best_s[tid][w], b)) b = best_s[tid][w];
+    partial[2 * blockIdx.x + tid] = b;
+  }
+}
+
+// the first minimum over the blocks' candidates; the record's indices, counts and scores
+__global__ __launch_bounds__(256) void ev_final_kernel(const EvBest* __restrict__ partial, int nblk, const uint64_t* __restrict__ keys,
+                                                        int want_dcf, air_eval_record* rec) {
+  __shared__ EvBest best_s[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  EvBest b[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (tid < nblk) {
+      b[q] = partial[2 * tid + q];
+    } else {
+      b[q].v = __longlong_as_double(0x7ff0000000000000ll);
+      b[q].k = 0xffffffffu;
+      b[q].rn = 0;
+    }
+    b[q] = ev_wave_best(b[q]);
+    if (lane == 0) best_s[q][wave] = b[q];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      EvBest m = best_s[q][0];
+      for (int w = 1; w < 4; ++w)
+        if (ev_better(best_s[q][w], m)) m = best_s[q][w];
+      b[q] = m;
+    }
+    const float s0 = ev_key_score(keys[0]);
+    // (an empty class makes every value NaN and leaves the index at its initial value: the record then says so
+    // through n_tar / n_non, and no key is read out of range)
+    const uint32_t n = rec->n_tar + rec->n_non;
+    rec->eer_idx = b[0].k;
+    rec->eer_rej_non = b[0].rn;
+    rec->eer_score_first = s0;
+    rec->eer_score_at = (b[0].k >= 1u && b[0].k <= n) ? ev_key_score(keys[b[0].k - 1u]) : s0;
+    rec->has_dcf = want_dcf ? 1u : 0u;
+    rec->dcf_idx = want_dcf ? b[1].k : 0u;
+    rec->dcf_rej_non = want_dcf ? b[1].rn : 0u;
+    rec->dcf_score_first = s0;
+    rec->dcf_score_at = (want_dcf && b[1].k >= 1u && b[1].k <= n) ? ev_key_score(keys[b[1].k - 1u]) : s0;
+  }
+}
+
+inline int ev_npad(int n) {
+  int p = EV_BLOCK;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+struct EvWs {
+  uint64_t* keys;
+  uint32_t* blockcnt;
+  EvBest* partial;
+};
+
+inline size_t ev_ws_bytes(int n) {
+  return (size_t)ev_npad(n) * 8 + (size_t)EV_MAX_BLOCKS * 4 + (size_t)EV_MAX_BLOCKS * 2 * sizeof(EvBest);
+}
+
+inline EvWs ev_ws(void* ws, int n) {
+  EvWs w;
+  char* p = static_cast<char*>(ws);
+  w.keys = reinterpret_cast<uint64_t*>(p);
+  p += (size_t)ev_npad(n) * 8;
+  w.blockcnt = reinterpret_cast<uint32_t*>(p);
+  p += (size_t)EV_MAX_BLOCKS * 4;
+  w.partial = reinterpret_cast<EvBest*>(p);
+  return w;
+}
+
+inline int ev_check(int n, const void* ws, size_t ws_bytes) {
+  if (n < 1 || ws == nullptr) return AIR_EINVAL;
+  if (n > EV_MAX_N) return AIR_EUNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AIR_EINVAL;
+  if (ws_bytes < ev_ws_bytes(n)) return AIR_EWORKSPACE;
+  return AIR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int air_eval_max_trials(void) { return EV_MAX_N; }
+int air_eval_sort_block(void) { return EV_BLOCK; }
+
+size_t air_eval_workspace_bytes(int n) { return (n < 1 || n > EV_MAX_N) ? 0 : ev_ws_bytes(n); }
+
+int air_eval_keys(const float* scores, const void* labels, int label_bytes, int n, int negate, air_eval_record* rec,
+                  void* ws, size_t ws_bytes, air_stream_t stream) {
+  if (!scores || !labels || !rec || (label_bytes != 4 && label_bytes != 8)) return AIR_EINVAL;
+  const int rc = ev_check(n, ws, ws_bytes);
+  if (rc != AIR_OK) return rc;
+  hipStream_t st = air_stream(stream);
+  const EvWs w = ev_ws(ws, n);
+  const int npad = ev_npad(n);
+  if (hipMemsetAsync(rec, 0, sizeof(air_eval_record), st) != hipSuccess) return AIR_ELAUNCH;
+  const int grid = npad / 1024;
+  if (label_bytes == 8)
+    ev_keys_kernel<int64_t><<<grid, 256, 0, st>>>(scores, static_cast<const int64_t*>(labels), n, npad, negate ? 1 : 0, w.keys, rec);
+  else
+    ev_keys_kernel<int32_t><<<grid, 256, 0, st>>>(scores, static_cast<const int32_t*>(labels), n, npad, negate ? 1 : 0, w.keys, rec);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream) {
+  const int rc = ev_check(n, ws, ws_bytes);
+  if (rc != AIR_OK) return rc;
+  hipStream_t st = air_stream(stream);
+  const EvWs w = ev_ws(ws, n);
+  const int npad = ev_npad(n);
+  const int nblk = npad / EV_BLOCK;
+  ev_sort_block_kernel<<<nblk, EV_THREADS, 0, st>>>(w.keys, 2, EV_BLOCK);
+  AIR_CHECK_LAUNCH();
+  for (int k = 2 * EV_BLOCK; k <= npad; k <<= 1) {
+    for (int j = k / 2; j >= EV_BLOCK; j >>= 1) {
+      ev_merge_global_kernel<<<npad / 2 / 256, 256, 0, st>>>(w.keys, npad, j, k);
+      AIR_CHECK_LAUNCH();
+    }
+    ev_sort_block_kernel<<<nblk, EV_THREADS, 0, st>>>(w.keys, k, k);
+    AIR_CHECK_LAUNCH();
+  }
+  return AIR_OK;
+}
+
+int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
+                       air_stream_t stream) {
+  if (!rec) return AIR_EINVAL;
+  const int rc = ev_check(n, ws, ws_bytes);
+  if (rc != AIR_OK) return rc;
+  hipStream_t st = air_stream(stream);
+  const EvWs w = ev_ws(ws, n);
+  const int nblk = (n + EV_BLOCK - 1) / EV_BLOCK;  // curve point k >= 1 goes with sorted trial k - 1, point 0 with trial 0
+  ev_counts_kernel<<<nblk, 256, 0, st>>>(w.keys, n, w.blockcnt, rec);
+  AIR_CHECK_LAUNCH();
+  ev_curve_kernel<<<nblk, EV_THREADS, 0, st>>>(w.keys, n, w.blockcnt, want_dcf ? 1 : 0, c1, c2, rec, w.partial);
+  AIR_CHECK_LAUNCH();
+  ev_final_kernel<<<1, 256, 0, st>>>(w.partial, nblk, w.keys, want_dcf ? 1 : 0, rec);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
+
+int air_eval_det_min(const float* scores, const void* labels, int label_bytes, int n, int negate, int want_dcf, double c1,
+                     double c2, air_eval_record* rec, void* ws, size_t ws_bytes, air_stream_t stream) {
+  int rc = air_eval_keys(scores, labels, label_bytes, n, negate, rec, ws, ws_bytes, stream);
+  if (rc != AIR_OK) return rc;
+  rc = air_eval_sort_keys(n, ws, ws_bytes, stream);
+  if (rc != AIR_OK) return rc;
+  return air_eval_curve_min(n, want_dcf, c1, c2, rec, ws, ws_bytes, stream);
+}
+
+}  // extern "C"

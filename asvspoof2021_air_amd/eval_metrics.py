@@ -5,7 +5,12 @@ Formulation: sort all trials by (score, class) with bona fide trials first among
 thresholds once - a threshold at the k-th sorted trial rejects the k lowest trials, so the false-rejection
 rate is the share of targets among them and the false-acceptance rate the share of non-targets above them.
 Equals the reference's curve (eval_metrics.py:19-46) point for point, ties included
-(tests/golden/eer.npz, 1e-12)."""
+(tests/golden/eer.npz, 1e-12).
+
+Beside it: host ports of the reference's t-DCF (eval_metrics.py:4-16, :49-193, evaluate_tDCF_asvspoof19.py) and the
+same minima of the curve found on the GPU for whole dev / eval passes (``*_device``: csrc/eval_metrics.hip sorts one
+integer key per trial, scans the class bit and reduces to the first minimum; the host finishes from integer counts,
+so every result is bit-equal to the host functions here or a ValueError).  DESIGN.md, "Evaluation on the device"."""
 import numpy as np
 
 
@@ -43,3 +48,190 @@ def eer_both_polarities(scores, labels):
     labels = np.asarray(labels)
     return min(compute_eer(scores[labels == 0], scores[labels == 1])[0],
                compute_eer(-scores[labels == 0], -scores[labels == 1])[0])
+
+
+# ------------------------------------------------------------------ t-DCF (host ports)
+def _asarray(x):
+    return np.asarray(x, dtype=np.float64).ravel()
+
+
+def obtain_asv_error_rates(tar_asv, non_asv, spoof_asv, asv_threshold):
+    """(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) of the ASV system at ``asv_threshold`` (eval_metrics.py:4-16);
+    Pmiss_spoof_asv is None when there are no spoof trials."""
+    tar_asv, non_asv, spoof_asv = _asarray(tar_asv), _asarray(non_asv), _asarray(spoof_asv)
+    Pfa_asv = np.sum(non_asv >= asv_threshold) / non_asv.size
+    Pmiss_asv = np.sum(tar_asv < asv_threshold) / tar_asv.size
+    Pmiss_spoof_asv = None if spoof_asv.size == 0 else np.sum(spoof_asv < asv_threshold) / spoof_asv.size
+    return Pfa_asv, Pmiss_asv, Pmiss_spoof_asv
+
+
+def asvspoof19_cost_model():
+    """The t-DCF parameters of the ASVspoof 2019 evaluation plan (evaluate_tDCF_asvspoof19.py:10-19)."""
+    Pspoof = 0.05
+    return {"Pspoof": Pspoof, "Ptar": (1 - Pspoof) * 0.99, "Pnon": (1 - Pspoof) * 0.01,
+            "Cmiss_asv": 1, "Cfa_asv": 10, "Cmiss_cm": 1, "Cfa_cm": 10}
+
+
+def tdcf_weights(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model):
+    """The weights (C1, C2) of the t-DCF curve with the reference's checks (eval_metrics.py:134-166); what it ends
+    the process for raises ValueError."""
+    cm = cost_model
+    if cm["Ptar"] < 0 or cm["Pnon"] < 0 or cm["Pspoof"] < 0 or np.abs(cm["Ptar"] + cm["Pnon"] + cm["Pspoof"] - 1) > 1e-10:
+        raise ValueError("the prior probabilities should be positive and sum up to one")
+    if Pmiss_spoof_asv is None:
+        raise ValueError("the miss rate of spoof tests against the ASV system is needed")
+    C1 = cm["Ptar"] * (cm["Cmiss_cm"] - cm["Cmiss_asv"] * Pmiss_asv) - cm["Pnon"] * cm["Cfa_asv"] * Pfa_asv
+    C2 = cm["Cfa_cm"] * cm["Pspoof"] * (1 - Pmiss_spoof_asv)
+    if C1 < 0 or C2 < 0 or np.isnan(C1) or np.isnan(C2):
+        raise ValueError("t-DCF cannot be evaluated with negative weights (C1 = %r, C2 = %r): check the ASV error rates" % (C1, C2))
+    return C1, C2
+
+
+def compute_tDCF(bonafide_score_cm, spoof_score_cm, Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model, print_cost=False):
+    """(tDCF_norm, CM_thresholds) over the n + 1 operating points of the countermeasure (eval_metrics.py:49-193);
+    higher scores support the bona fide hypothesis."""
+    C1, C2 = tdcf_weights(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model)
+    bona, spoof = _asarray(bonafide_score_cm), _asarray(spoof_score_cm)
+    combined = np.concatenate((bona, spoof))
+    if np.isnan(combined).any() or np.isinf(combined).any():
+        raise ValueError("the scores contain nan or inf")
+    if np.unique(combined).size < 3:
+        raise ValueError("soft CM scores are needed, not binary decisions")
+    Pmiss_cm, Pfa_cm, CM_thresholds = compute_det_curve(bona, spoof)
+    tDCF = C1 * Pmiss_cm + C2 * Pfa_cm
+    tDCF_norm = tDCF / np.minimum(C1, C2)
+    if print_cost:
+        print("t-DCF evaluation from [Nbona={}, Nspoof={}] trials\n".format(bona.size, spoof.size))
+        if C2 == np.minimum(C1, C2):
+            print("   tDCF_norm(s) = {:8.5f} x Pmiss_cm(s) + Pfa_cm(s)\n".format(C1 / C2))
+        else:
+            print("   tDCF_norm(s) = Pmiss_cm(s) + {:8.5f} x Pfa_cm(s)\n".format(C2 / C1))
+    return tDCF_norm, CM_thresholds
+
+
+def compute_eer_and_tdcf(cm_score_file, asv_score_file):
+    """(min EER over both polarities, min t-DCF of the polarity with the lower EER) of a CM score file
+    ``utt source key score`` against the organisers' ASV score file ``source key score``
+    (evaluate_tDCF_asvspoof19.py:6-67, :120, without the plots)."""
+    asv = np.genfromtxt(asv_score_file, dtype=str)
+    asv_keys, asv_scores = asv[:, 1], asv[:, 2].astype(np.float64)
+    cm = np.genfromtxt(cm_score_file, dtype=str)
+    cm_keys, cm_scores = cm[:, 2], cm[:, 3].astype(np.float64)
+    tar_asv, non_asv, spoof_asv = (asv_scores[asv_keys == k] for k in ("target", "nontarget", "spoof"))
+    bona_cm, spoof_cm = cm_scores[cm_keys == "bonafide"], cm_scores[cm_keys == "spoof"]
+    _, asv_threshold = compute_eer(tar_asv, non_asv)
+    eer_cm = compute_eer(bona_cm, spoof_cm)[0]
+    other_eer_cm = compute_eer(-bona_cm, -spoof_cm)[0]
+    rates = obtain_asv_error_rates(tar_asv, non_asv, spoof_asv, asv_threshold)
+    if eer_cm < other_eer_cm:
+        curve, _ = compute_tDCF(bona_cm, spoof_cm, *rates, asvspoof19_cost_model())
+    else:
+        curve, _ = compute_tDCF(-bona_cm, -spoof_cm, *rates, asvspoof19_cost_model())
+    return min(eer_cm, other_eer_cm), float(curve[np.argmin(curve)])
+
+
+# ------------------------------------------------------------------ on the device (csrc/eval_metrics.hip)
+_RECORD = np.dtype([("n_tar", "<u4"), ("n_non", "<u4"), ("n_nan", "<u4"), ("n_inf", "<u4"), ("n_distinct", "<u4"),
+                    ("has_dcf", "<u4"), ("eer_idx", "<u4"), ("eer_rej_non", "<u4"), ("eer_score_first", "<f4"),
+                    ("eer_score_at", "<f4"), ("dcf_idx", "<u4"), ("dcf_rej_non", "<u4"), ("dcf_score_first", "<f4"),
+                    ("dcf_score_at", "<f4"), ("reserved", "<u4", (2,))])  # air_eval_record (include/air_hip.h)
+
+
+def _rates(rec, which):
+    """(frr, far, threshold, k) at the record's EER / t-DCF point, from its integer counts as compute_det_curve has them."""
+    k, rn = int(rec[which + "_idx"]), int(rec[which + "_rej_non"])
+    n_tar, n_non = int(rec["n_tar"]), int(rec["n_non"])
+    frr = np.float64(k - rn) / np.float64(n_tar)
+    far = np.float64(n_non - rn) / np.float64(n_non)
+    thr = np.float64(rec[which + "_score_at"]) if k > 0 else np.float64(rec[which + "_score_first"]) - 0.001
+    return frr, far, float(thr), k
+
+
+def _check_record(rec, tdcf=False):
+    if int(rec["n_nan"]) > 0:
+        raise ValueError("%d scores are NaN" % int(rec["n_nan"]))
+    if int(rec["n_tar"]) == 0 or int(rec["n_non"]) == 0:
+        raise ValueError("both classes need trials (bona fide: %d, spoof: %d)" % (int(rec["n_tar"]), int(rec["n_non"])))
+    if tdcf:
+        if int(rec["n_inf"]) > 0:
+            raise ValueError("the scores contain nan or inf")
+        if int(rec["n_distinct"]) < 3:
+            raise ValueError("soft CM scores are needed, not binary decisions")
+
+
+class DeviceCurveMinima:
+    """The enqueued device metrics of one score set: one air_eval_record per polarity in ``records`` ((P, 16) int32 on
+    the GPU; the rows of ``out`` when the caller packs them with other results of a pass).  Nothing has been copied
+    or synchronised until ``fetch()`` / ``result()``."""
+
+    def __init__(self, scores, labels, negates, weights=None, out=None):
+        import torch
+        from . import ops
+        if not (torch.is_tensor(scores) and scores.is_cuda and torch.is_tensor(labels) and labels.is_cuda):
+            raise ValueError("the device metrics take GPU tensors (compute_eer is the host path)")
+        if scores.dtype != torch.float32:
+            raise ValueError("scores must be fp32, got %s" % scores.dtype)
+        scores, labels = scores.reshape(-1).contiguous(), labels.reshape(-1).contiguous()
+        self.negates = tuple(bool(n) for n in negates)
+        self.weights = weights
+        self.records = out if out is not None else torch.empty(len(self.negates), ops.EVAL_RECORD_WORDS, dtype=torch.int32,
+                                                               device=scores.device)
+        ws = torch.empty(ops.eval_workspace_bytes(scores.numel()), dtype=torch.uint8, device=scores.device)
+        c1, c2 = (None, None) if weights is None else (float(weights[0]), float(weights[1]))
+        for row, neg in zip(self.records, self.negates):  # back to back on the stream, sharing the scratch
+            ops.eval_det_min(scores, labels, row, ws, negate=neg, c1=c1, c2=c2)
+        self._host = None
+
+    def fetch(self, host_words=None):
+        """The single device-to-host copy (or the caller's copy of the packed ``out``, as int32 words)."""
+        if self._host is None:
+            words = self.records.cpu().numpy() if host_words is None else np.asarray(host_words)
+            self._host = np.ascontiguousarray(words, dtype=np.int32).reshape(-1).view(_RECORD)
+        return self._host
+
+    def eer(self, i=0):
+        """(eer, threshold) of polarity i, finished on the host as compute_eer does."""
+        rec = self.fetch()[i]
+        _check_record(rec)
+        frr, far, thr, _ = _rates(rec, "eer")
+        return float((frr + far) / 2.0), thr
+
+    def min_tdcf(self, i=0):
+        """(min t-DCF, index of the operating point) of polarity i: the device's argmin, the value recomputed from the
+        counts with the host formula of compute_tDCF."""
+        rec = self.fetch()[i]
+        _check_record(rec, tdcf=True)
+        C1, C2 = self.weights
+        frr, far, _, k = _rates(rec, "dcf")
+        return float((C1 * frr + C2 * far) / np.minimum(C1, C2)), k
+
+
+class _Pending:
+    def __init__(self, minima, finish):
+        self.minima, self._finish = minima, finish
+
+    def result(self, refresh=False):
+        """``refresh``: copy the records again (the enqueued work was captured in a graph and replayed since)."""
+        if refresh:
+            self.minima._host = None
+        return self._finish(self.minima)
+
+
+def compute_eer_device(scores, labels, negate=False):
+    """compute_eer(scores[labels == 0], scores[labels != 0]) (of -scores with ``negate``) for fp32 scores and integer
+    labels on the GPU, up to 2^20 trials: enqueued on the current stream; ``.result()`` makes the one device-to-host
+    copy and returns (eer, threshold), bit-equal to compute_eer's.  ValueError for NaN scores or an empty class."""
+    return _Pending(DeviceCurveMinima(scores, labels, (negate,)), lambda m: m.eer(0))
+
+
+def eer_both_polarities_device(scores, labels):
+    """eer_both_polarities on the GPU: both polarities enqueued back to back, one host copy in ``.result()``."""
+    return _Pending(DeviceCurveMinima(scores, labels, (False, True)), lambda m: min(m.eer(0)[0], m.eer(1)[0]))
+
+
+def min_tdcf_device(scores, labels, Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model, negate=False):
+    """min and argmin of compute_tDCF(scores[labels == 0], scores[labels != 0], ...)[0] on the GPU: the host computes
+    and checks the weights, the device finds the first minimum of the curve; ``.result()`` -> (min t-DCF, index).
+    NaN / inf scores, fewer than three distinct scores or an empty class raise ValueError there."""
+    weights = tdcf_weights(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model)
+    return _Pending(DeviceCurveMinima(scores, labels, (negate,), weights), lambda m: m.min_tdcf(0))

@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import ops
+from .devbuf import DeviceVector
 from .feature_extraction import LFCC
 
 
@@ -90,16 +91,22 @@ class GraphedScorer:
 
 @torch.no_grad()
 def test_on_dataset(model, loader, score_file, loss_model=None, add_loss=None, task="19eval", ecapa=False,
-                    device="cuda", keep_dataset_labels=False, use_graph=False):
+                    device="cuda", keep_dataset_labels=False, use_graph=False, sync="batch"):
     """generate_score.py:75-119 over any iterable of dataset batches
     ``(lfcc:(B,1,feat_len,60), audio_fn, tag, labels[, channel])`` ('19' tasks) or
     ``(lfcc, audio_fn)`` (2021 LA/DF eval).  Returns the number of lines written.
-    use_graph: replay a captured hipGraph per batch shape (GraphedScorer) - for the reference's batch size 1."""
+    use_graph: replay a captured hipGraph per batch shape (GraphedScorer) - for the reference's batch size 1.
+    sync: "batch" copies each batch's scores to the host before the next is launched (one device synchronisation per
+    utterance at the reference's batch size 1); "end" keeps them in a device buffer and writes the file after ONE
+    copy - the same text, byte for byte."""
+    if sync not in ("batch", "end"):
+        raise ValueError("sync must be 'batch' or 'end', got %r" % (sync,))
     model.eval()
     os.makedirs(os.path.dirname(os.path.abspath(score_file)), exist_ok=True)
     is19 = "19" in task
     n = 0
     graphs = {}
+    held, rows = None, []  # sync="end": the scores on the device, (name, label) per line on the host
     with open(score_file, "w") as fh:
         for data in loader:
             if is19:
@@ -118,6 +125,13 @@ def test_on_dataset(model, loader, score_file, loss_model=None, add_loss=None, t
                 score = graphs[key](lfcc)
             else:
                 score = batch_scores(model, lfcc, loss_model, add_loss)
+            if sync == "end":
+                if held is None:
+                    held = DeviceVector(torch.float32, lfcc.device, (len(loader) if hasattr(loader, "__len__") else 64) * lfcc.shape[0])
+                held.append((-score).float())  # (a copy: a GraphedScorer's output is overwritten by the next replay)
+                rows.extend((audio_fn[j], (int(labels[j]) if keep_dataset_labels else 0) if is19 else None)
+                            for j in range(lfcc.shape[0]))
+                continue
             vals = (-score).float().cpu().tolist()
             for j, v in enumerate(vals):
                 if is19:
@@ -125,6 +139,10 @@ def test_on_dataset(model, loader, score_file, loss_model=None, add_loss=None, t
                     fh.write(format_score_line(audio_fn[j], v, "spoof" if lab else "bonafide"))
                 else:
                     fh.write(format_score_line(audio_fn[j], v))
+                n += 1
+        if held is not None:
+            for (name, lab), v in zip(rows, held.view().cpu().tolist()):
+                fh.write(format_score_line(name, v, None if lab is None else ("spoof" if lab else "bonafide")))
                 n += 1
     return n
 

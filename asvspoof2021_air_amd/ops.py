@@ -1202,6 +1202,63 @@ def softmax_rows(logits):
     return probs
 
 
+# ---------------------------------------------------------------- evaluation metrics (csrc/eval_metrics.hip)
+EVAL_MAX_TRIALS = 1 << 20
+EVAL_RECORD_WORDS = 16  # air_eval_record as int32 words
+
+
+def eval_workspace_bytes(n):
+    """Bytes of scratch the evaluation-metric calls need for n trials (ValueError beyond EVAL_MAX_TRIALS)."""
+    n = int(n)
+    if n < 1 or n > EVAL_MAX_TRIALS:
+        raise ValueError("device metrics take 1 .. %d trials, got %d" % (EVAL_MAX_TRIALS, n))
+    return int(_hip.lib().air_eval_workspace_bytes(ci(n)))
+
+
+def _eval_args(scores, labels, ws, record=None):
+    if not (torch.is_tensor(scores) and torch.is_tensor(labels)):
+        raise _hip.AirError("scores and labels must be GPU tensors (the HIP path has no CPU fallback)")
+    if scores.dim() != 1 or labels.dim() != 1 or labels.numel() != scores.numel():
+        raise ValueError("scores and labels must be 1-d and of one length, got %s and %s" % (
+            tuple(scores.shape), tuple(labels.shape)))
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise _hip.AirError("labels must be int32 or int64, got %s" % labels.dtype)
+    n = scores.numel()
+    need = eval_workspace_bytes(n)
+    if ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (eval_workspace_bytes)" % need)
+    if record is not None and (record.dtype != torch.int32 or record.numel() != EVAL_RECORD_WORDS):
+        raise ValueError("record must be %d int32 words" % EVAL_RECORD_WORDS)
+    return n
+
+
+def eval_det_min(scores, labels, record, ws, negate=False, c1=None, c2=None):
+    """EER point (and, with the fp64 weights c1, c2, the min t-DCF point) of the DET curve of ``scores`` (fp32, (n,))
+    and ``labels`` (int32 | int64, 0 = bona fide) into ``record`` (EVAL_RECORD_WORDS int32: air_eval_record), using the
+    uint8 scratch ``ws``.  Enqueues only: nothing is allocated or synchronised."""
+    n = _eval_args(scores, labels, ws, record)
+    want = c1 is not None
+    _hip.check(_hip.lib().air_eval_det_min(
+        dptr(scores), dptr(labels, labels.dtype), ci(labels.element_size()), ci(n), ci(1 if negate else 0),
+        ci(1 if want else 0), ctypes.c_double(c1 if want else 1.0), ctypes.c_double(c2 if want else 1.0),
+        dptr(record, torch.int32), dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_eval_det_min")
+    return record
+
+
+def eval_sorted_keys(scores, labels, negate=False):
+    """The n sorted composite keys ((ordered image of the score) << 1 | is_spoof) as an int64 GPU tensor, and the
+    record with the class / NaN / inf counts - the first two steps of eval_det_min, for tests of the sort."""
+    ws = torch.empty(eval_workspace_bytes(scores.numel()), dtype=torch.uint8, device=scores.device)
+    record = torch.empty(EVAL_RECORD_WORDS, dtype=torch.int32, device=scores.device)
+    n = _eval_args(scores, labels, ws, record)
+    L = _hip.lib()
+    _hip.check(L.air_eval_keys(dptr(scores), dptr(labels, labels.dtype), ci(labels.element_size()), ci(n),
+                               ci(1 if negate else 0), dptr(record, torch.int32), dptr(ws, torch.uint8), csz(ws.numel()),
+                               stream()), "air_eval_keys")
+    _hip.check(L.air_eval_sort_keys(ci(n), dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_eval_sort_keys")
+    return ws[:n * 8].view(torch.int64).clone(), record
+
+
 # BatchNorm's num_batches_tracked counters: one multi-tensor add per forward instead of one 4 us ATen launch per
 # layer (34 per ECAPA step).  bn_tick() queues a counter, bn_flush() adds 1 to everything queued since the last flush.
 _TICKS = []

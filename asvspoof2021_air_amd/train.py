@@ -12,6 +12,7 @@ The head is ``add_loss`` (main_train.py:66-67, :250-300): ``"ang_iso"`` (OC-Soft
 ``None`` (the reference's default: cross-entropy on the model's logits, no loss module), ``"isolate"`` /
 ``"iso_sq"`` (IsolateLoss / IsolateSquareLoss on the features) or ``"p2sgrad"`` (P2SGradLoss on the features).
 """
+import collections
 import os
 
 import numpy as np
@@ -32,6 +33,10 @@ def adjust_learning_rate(lr0, optimizer, epoch_num, lr_decay=0.5, interval=30):
         group["lr"] = lr
     return lr
 
+
+# what Trainer.evaluate returns: the monitored loss, the EER (min over both polarities), the min t-DCF (None without
+# ``tdcf``) and the pass's scores and labels, still on the device
+EvalResult = collections.namedtuple("EvalResult", ("loss", "eer", "min_tdcf", "scores", "labels"))
 
 ADD_LOSSES = (None, "isolate", "iso_sq", "ang_iso", "p2sgrad")
 # the head a given loss module stands for (any other module: the OC-Softmax head's interface, as before)
@@ -302,6 +307,59 @@ class Trainer:
             return ops.isolate_fwd(feats.float().contiguous(), lm.center.detach().contiguous(), labels, float(lm.r_real),
                                    float(lm.r_fake), self.add_loss == "iso_sq", want_dist=True)
         return self.loss(feats, labels)
+
+    @torch.no_grad()
+    def evaluate(self, batches, epoch_num=None, log=None, capacity=None, tdcf=None):
+        """The dev / eval half of the reference's epoch (main_train.py:484-668) over ``batches``, an iterable of
+        ``(pcm, labels[, start[, lengths]])`` as eval_batch takes them, without a host synchronisation inside the
+        loop: per batch eval_batch, the loss into a device vector, scores and labels into device buffers
+        (preallocated for ``capacity`` trials, or from ``len(batches)`` where it has one; grown by device-side copies
+        otherwise).  Behind the loop the EER of both score polarities (main_train.py:662-664) and, with
+        ``tdcf=(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model)``, the min t-DCF of the polarity with the lower
+        EER (evaluate_tDCF_asvspoof19.py:53-67) are found on the device (eval_metrics.DeviceCurveMinima) and fetched
+        with the loss vector in ONE copy; the monitored loss is ``np.nanmean`` of the per-batch losses on the host
+        (main_train.py:671 - a device mean would not reproduce numpy's summation order).  ``log``: "dev_loss.log" or
+        "test_loss.log" - the line log_eval writes for ``epoch_num``.  Bit-equal to the per-batch loop
+        (``eval_batch`` + ``.item()``, ``np.nanmean``, ``eval_metrics.eer_both_polarities``).  Up to 2^20 trials.
+        world > 1: every rank evaluates what it is given; no collective runs.  Returns an EvalResult
+        (loss, eer, min_tdcf or None, the device score and label tensors)."""
+        from .devbuf import DeviceVector
+        from .eval_metrics import DeviceCurveMinima, tdcf_weights
+        from .ops import EVAL_RECORD_WORDS
+        if log not in (None, "dev_loss.log", "test_loss.log"):
+            raise ValueError("log must be None, 'dev_loss.log' or 'test_loss.log', got %r" % (log,))
+        weights = tdcf_weights(*tdcf) if tdcf is not None else None  # (refused before the pass, not after it)
+        n_batches = len(batches) if hasattr(batches, "__len__") else None
+        losses = scores = labs = None
+        for batch in batches:
+            pcm = batch[0]
+            labels = batch[1].to(device=self.device, dtype=torch.int64, non_blocking=True).contiguous()
+            loss, score = self.eval_batch(pcm, labels, batch[2] if len(batch) > 2 else None,
+                                          batch[3] if len(batch) > 3 else None)
+            if losses is None:
+                trials = capacity if capacity is not None else (n_batches or 0) * pcm.shape[0]
+                losses = DeviceVector(torch.float32, self.device, n_batches or 64)
+                scores = DeviceVector(torch.float32, self.device, trials)
+                labs = DeviceVector(torch.int64, self.device, trials)
+            losses.append(loss)
+            scores.append(score)
+            labs.append(labels)
+        if losses is None:
+            raise ValueError("evaluate() needs at least one batch")
+        words = 2 * EVAL_RECORD_WORDS
+        pack = torch.empty(words + losses.n, dtype=torch.int32, device=self.device)  # [records | losses]: one fetch
+        minima = DeviceCurveMinima(scores.view(), labs.view(), (False, True), weights,
+                                   out=pack[:words].view(2, EVAL_RECORD_WORDS))
+        pack[words:].view(torch.float32).copy_(losses.view())
+        host = pack.cpu().numpy()
+        minima.fetch(host[:words])
+        batch_losses = host[words:].view(np.float32).astype(np.float64)  # what .item() per batch would have listed
+        eers = (minima.eer(0)[0], minima.eer(1)[0])
+        eer = min(eers)
+        min_tdcf = minima.min_tdcf(0 if eers[0] < eers[1] else 1)[0] if weights is not None else None
+        if log is not None:
+            self.log_eval(epoch_num, batch_losses, eer, name=log)
+        return EvalResult(float(np.nanmean(batch_losses)), eer, min_tdcf, scores.view(), labs.view())
 
     def step(self, pcm, labels, start=None, lengths=None):
         """``lengths`` None: a batch of one length; a ``start`` forces the eager step.  ``lengths`` int32 (B,): a ragged

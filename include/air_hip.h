@@ -998,6 +998,51 @@ int air_isolate_bwd(const float* x, const float* center, const int64_t* labels, 
 int air_amsoftmax_fwd(const float* x, const float* centers, const int64_t* labels, int B, int D, int C, float s,
                       float m, float* logits, float* margin_logits, air_stream_t stream);
 
+/* --------------------------------------------------- evaluation metrics ---
+ * The two minima the reference reads off the DET curve of a dev / eval pass, exactly, without leaving the stream:
+ * the EER point of compute_eer (eval_metrics.py:19-46: mergesort, cumsum, argmin |frr - far|; called on both score
+ * polarities at main_train.py:662-664) and the min t-DCF point (the argmin of evaluate_tDCF_asvspoof19.py:58-59 over
+ * the curve of compute_tDCF, eval_metrics.py:157-172).  scores: n fp32; labels: n integers of label_bytes (4 | 8)
+ * bytes, 0 = bona fide, anything else = spoof; negate != 0 evaluates -scores.  n <= air_eval_max_trials() (2^20),
+ * more: AIR_EUNSUPPORTED.  No allocation, no host synchronisation: all scratch is the caller's workspace of
+ * air_eval_workspace_bytes(n) bytes (0: n out of range; 16-byte aligned), everything is enqueued on `stream`.
+ *
+ * Per trial one 64-bit key ((order-preserving image of the score) << 1 | is_spoof, -0.0 taken as +0.0), padded with
+ * all-ones sentinels to a power of two >= air_eval_sort_block() and sorted ascending by a bitonic network; the
+ * inclusive scan of the class bit gives rejected_non[k] (and rejected_tar[k] = k - rejected_non[k]) after the k lowest
+ * trials, k = 0 .. n; in fp64, frr = rejected_tar / n_tar, far = (n_non - rejected_non) / n_non, and the record gets
+ * the FIRST k that minimises |frr - far| and, with want_dcf, the FIRST k that minimises
+ * (c1 * frr + c2 * far) / min(c1, c2) (c1, c2: the C1, C2 of eval_metrics.py:160-162, computed by the caller).
+ * The caller finishes on the host from the integer counts; it must refuse n_nan > 0 (numpy sorts NaN last) and an
+ * empty class (the indices are then meaningless). */
+typedef struct air_eval_record {
+  uint32_t n_tar, n_non;          /* bona fide / spoof trials */
+  uint32_t n_nan, n_inf;          /* NaN / +-inf scores (compute_tDCF refuses both, eval_metrics.py:147-149) */
+  uint32_t n_distinct;            /* distinct scores (compute_tDCF refuses < 3, eval_metrics.py:152-154) */
+  uint32_t has_dcf;               /* the dcf_* fields are valid */
+  uint32_t eer_idx, eer_rej_non;  /* k of the EER point, rejected_non[k] */
+  float eer_score_first;          /* sorted score 0 */
+  float eer_score_at;             /* sorted score k - 1 (score 0 when k = 0) */
+  uint32_t dcf_idx, dcf_rej_non;
+  float dcf_score_first, dcf_score_at;
+  uint32_t reserved[2];
+} air_eval_record; /* 64 bytes */
+int air_eval_max_trials(void);
+int air_eval_sort_block(void); /* keys sorted per workgroup in LDS: the block boundary of the network */
+size_t air_eval_workspace_bytes(int n);
+/* The whole chain: keys, sort, curve minima.  c1, c2 are read only with want_dcf. */
+int air_eval_det_min(const float* scores, const void* labels, int label_bytes, int n, int negate, int want_dcf,
+                     double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes, air_stream_t stream);
+/* Its three steps on the same workspace (the keys are its first npad * 8 bytes): air_eval_keys zeroes the record,
+ * builds the padded keys and counts n_tar / n_non / n_nan / n_inf; air_eval_sort_keys sorts them (np.sort of the keys,
+ * eval_metrics.py:26 up to the order of equal keys); air_eval_curve_min needs the record and the sorted keys of the
+ * first two. */
+int air_eval_keys(const float* scores, const void* labels, int label_bytes, int n, int negate, air_eval_record* rec,
+                  void* ws, size_t ws_bytes, air_stream_t stream);
+int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
+                       air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

@@ -10,7 +10,10 @@ Equals the reference's curve (eval_metrics.py:19-46) point for point, ties inclu
 Beside it: host ports of the reference's t-DCF (eval_metrics.py:4-16, :49-193, evaluate_tDCF_asvspoof19.py) and the
 same minima of the curve found on the GPU for whole dev / eval passes (``*_device``: csrc/eval_metrics.hip sorts one
 integer key per trial, scans the class bit and reduces to the first minimum; the host finishes from integer counts,
-so every result is bit-equal to the host functions here or a ValueError).  DESIGN.md, "Evaluation on the device"."""
+so every result is bit-equal to the host functions here or a ValueError).  DESIGN.md, "Evaluation on the device".
+
+``*_by_group``: the same figures per spoofing attack or per channel condition, from a group id per trial (-1 = member of
+every group) - on the host as a loop over the subsets, on the device from the one sort (``*_by_group_device``)."""
 import numpy as np
 
 
@@ -130,6 +133,109 @@ def compute_eer_and_tdcf(cm_score_file, asv_score_file):
     return min(eer_cm, other_eer_cm), float(curve[np.argmin(curve)])
 
 
+# ------------------------------------------------------------------ breakdown by attack / by channel condition
+# Every trial carries an integer group id: g in 0 .. n_groups - 1 puts it into group g, -1 into EVERY group.  Per-attack
+# table: bona fide trials -1, spoof trials their attack index.  Per-channel table: every trial its condition.  Group g's
+# result is BY DEFINITION what the pooled functions above return for the subset {i : g_i == g or g_i == -1}; a group
+# without bona fide or without spoof trials (a dev set that lacks the attack) gives None.
+def _checked_groups(groups, n_groups, n):
+    groups = np.asarray(groups).ravel()
+    n_groups = int(n_groups)
+    if n_groups < 1:
+        raise ValueError("n_groups must be at least 1, got %d" % n_groups)
+    if groups.size != n or not np.issubdtype(groups.dtype, np.integer):
+        raise ValueError("groups must be %d integers" % n)
+    bad = int(np.count_nonzero((groups < -1) | (groups >= n_groups)))
+    if bad:
+        raise ValueError("%d group ids lie outside -1 .. %d" % (bad, n_groups - 1))
+    return groups, n_groups
+
+
+def _subsets(scores, labels, groups, n_groups):
+    """Per group the (bona fide scores, spoof scores) of its subset; label 0 = bona fide, anything else = spoof."""
+    scores = _asarray(scores)
+    labels = np.asarray(labels).ravel()
+    groups, n_groups = _checked_groups(groups, n_groups, scores.size)
+    for g in range(n_groups):
+        member = (groups == g) | (groups == -1)
+        yield scores[member & (labels == 0)], scores[member & (labels != 0)]
+
+
+def _rates_of_group(rates_by_group, n_groups):
+    """n_groups triples (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) from one triple for all groups or one per group."""
+    rates = list(rates_by_group)
+    if len(rates) == 3 and not any(isinstance(r, (tuple, list, np.ndarray)) for r in rates):
+        return [tuple(rates)] * n_groups
+    if len(rates) != n_groups or any(len(r) != 3 for r in rates):
+        raise ValueError("rates_by_group must be one (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) or one per group (%d)" % n_groups)
+    return [tuple(r) for r in rates]
+
+
+def compute_eer_by_group(scores, labels, groups, n_groups):
+    """[compute_eer of group g's subset, or None where it lacks a class] for g in 0 .. n_groups - 1."""
+    return [compute_eer(tar, non) if tar.size and non.size else None for tar, non in _subsets(scores, labels, groups, n_groups)]
+
+
+def eer_both_polarities_by_group(scores, labels, groups, n_groups):
+    """Per group the lower of the two polarities' EERs (eer_both_polarities of its subset), or None."""
+    scores = _asarray(scores)
+    pos = compute_eer_by_group(scores, labels, groups, n_groups)
+    neg = compute_eer_by_group(-scores, labels, groups, n_groups)
+    return [None if p is None else min(p[0], q[0]) for p, q in zip(pos, neg)]
+
+
+def min_tdcf_by_group(scores, labels, groups, n_groups, rates_by_group, cost_model):
+    """Per group (min, argmin) of compute_tDCF over its subset's curve, or None where the subset lacks a class.
+    ``rates_by_group``: one (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) for all groups or one per group (a per-attack table
+    takes Pmiss_spoof_asv from that attack's ASV trials).  What compute_tDCF refuses raises here too."""
+    rates = _rates_of_group(rates_by_group, int(n_groups))
+    for r in rates:
+        tdcf_weights(*r, cost_model)  # (refused before any curve is walked)
+    out = []
+    for (tar, non), r in zip(_subsets(scores, labels, groups, n_groups), rates):
+        if not (tar.size and non.size):
+            out.append(None)
+            continue
+        curve, _ = compute_tDCF(tar, non, *r, cost_model)
+        k = int(np.argmin(curve))
+        out.append((float(curve[k]), k))
+    return out
+
+
+def compute_eer_and_tdcf_by_source(cm_score_file, asv_score_file):
+    """compute_eer_and_tdcf broken down by the ``source`` column of the CM score file ``utt source key score``:
+    ({source: (eer, min_tdcf)}, (pooled eer, pooled min_tdcf)).  A source is an attack: its subset is every bona fide
+    trial plus its own spoof trials.  The ASV threshold, Pfa_asv and Pmiss_asv are the pooled ones, Pmiss_spoof_asv is
+    taken over the ASV rows of that source, and every entry uses the ONE polarity that wins the pooled EER."""
+    asv = np.genfromtxt(asv_score_file, dtype=str)
+    asv_src, asv_keys, asv_scores = asv[:, 0], asv[:, 1], asv[:, 2].astype(np.float64)
+    cm = np.genfromtxt(cm_score_file, dtype=str)
+    cm = cm[(cm[:, 2] == "bonafide") | (cm[:, 2] == "spoof")]
+    cm_src, cm_keys, cm_scores = cm[:, 1], cm[:, 2], cm[:, 3].astype(np.float64)
+    tar_asv, non_asv, spoof_asv = (asv_scores[asv_keys == k] for k in ("target", "nontarget", "spoof"))
+    bona_cm, spoof_cm = cm_scores[cm_keys == "bonafide"], cm_scores[cm_keys == "spoof"]
+    _, asv_threshold = compute_eer(tar_asv, non_asv)
+    eer_cm = compute_eer(bona_cm, spoof_cm)[0]
+    other_eer_cm = compute_eer(-bona_cm, -spoof_cm)[0]
+    Pfa_asv, Pmiss_asv, Pmiss_spoof_asv = obtain_asv_error_rates(tar_asv, non_asv, spoof_asv, asv_threshold)
+    sign = 1.0 if eer_cm < other_eer_cm else -1.0
+    curve, _ = compute_tDCF(sign * bona_cm, sign * spoof_cm, Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, asvspoof19_cost_model())
+    pooled = (min(eer_cm, other_eer_cm), float(curve[np.argmin(curve)]))
+    sources = sorted(set(cm_src[cm_keys == "spoof"].tolist()))
+    if not sources:
+        return {}, pooled
+    labels = (cm_keys == "spoof").astype(np.int64)
+    groups = np.full(cm_scores.size, -1, dtype=np.int64)
+    rates = []
+    for g, src in enumerate(sources):
+        groups[(labels == 1) & (cm_src == src)] = g
+        of_src = asv_scores[(asv_keys == "spoof") & (asv_src == src)]
+        rates.append((Pfa_asv, Pmiss_asv, obtain_asv_error_rates(tar_asv, non_asv, of_src, asv_threshold)[2]))
+    eers = compute_eer_by_group(sign * cm_scores, labels, groups, len(sources))
+    tdcfs = min_tdcf_by_group(sign * cm_scores, labels, groups, len(sources), rates, asvspoof19_cost_model())
+    return {src: (eers[g][0], tdcfs[g][0]) for g, src in enumerate(sources)}, pooled
+
+
 # ------------------------------------------------------------------ on the device (csrc/eval_metrics.hip)
 _RECORD = np.dtype([("n_tar", "<u4"), ("n_non", "<u4"), ("n_nan", "<u4"), ("n_inf", "<u4"), ("n_distinct", "<u4"),
                     ("has_dcf", "<u4"), ("eer_idx", "<u4"), ("eer_rej_non", "<u4"), ("eer_score_first", "<f4"),
@@ -235,3 +341,90 @@ def min_tdcf_device(scores, labels, Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_mo
     NaN / inf scores, fewer than three distinct scores or an empty class raise ValueError there."""
     weights = tdcf_weights(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model)
     return _Pending(DeviceCurveMinima(scores, labels, (negate,), weights), lambda m: m.min_tdcf(0))
+
+
+# ------------------------------------------------------------------ the breakdown on the device
+class DeviceGroupedMinima:
+    """DeviceCurveMinima for the pooled trials and every group from one sort per polarity (air_eval_det_min_grouped):
+    ``records`` is (P, n_groups + 1, 16) int32 on the GPU (``out`` when the caller packs it with other results), row 0
+    of a polarity the pooled record, row 1 + g group g's - what the ungrouped kernel writes for that subset alone.
+    ``weights``: None or (n_groups + 1, 2) t-DCF weights (C1, C2) per record.  Nothing has been copied back or
+    synchronised until ``fetch()`` / ``result()``; ids outside -1 .. n_groups - 1 raise ValueError there."""
+
+    def __init__(self, scores, labels, groups, n_groups, negates, weights=None, out=None):
+        import torch
+        from . import ops
+        if not all(torch.is_tensor(t) and t.is_cuda for t in (scores, labels, groups)):
+            raise ValueError("the device metrics take GPU tensors (compute_eer_by_group is the host path)")
+        if scores.dtype != torch.float32:
+            raise ValueError("scores must be fp32, got %s" % scores.dtype)
+        scores, labels, groups = (t.reshape(-1).contiguous() for t in (scores, labels, groups))
+        self.n_groups = int(n_groups)
+        self.negates = tuple(bool(n) for n in negates)
+        shape = (len(self.negates), self.n_groups + 1, ops.EVAL_RECORD_WORDS)
+        ws = torch.empty(ops.eval_workspace_bytes_grouped(scores.numel(), self.n_groups), dtype=torch.uint8, device=scores.device)
+        self.weights = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(self.n_groups + 1, 2)
+        c12 = None if weights is None else torch.from_numpy(self.weights).to(scores.device)
+        self.records = out.view(shape) if out is not None else torch.empty(shape, dtype=torch.int32, device=scores.device)
+        for rows, neg in zip(self.records, self.negates):  # back to back on the stream, sharing the scratch
+            ops.eval_det_min_grouped(scores, labels, groups, self.n_groups, rows, ws, negate=neg, c12=c12)
+        self._host = None
+
+    def fetch(self, host_words=None):
+        """The single device-to-host copy (or the caller's copy of the packed ``out``, as int32 words)."""
+        if self._host is None:
+            words = self.records.cpu().numpy() if host_words is None else np.asarray(host_words)
+            host = np.ascontiguousarray(words, dtype=np.int32).reshape(-1).view(_RECORD).reshape(len(self.negates), self.n_groups + 1)
+            bad = int(host[0, 0]["reserved"][0])
+            if bad:
+                raise ValueError("%d group ids lie outside -1 .. %d" % (bad, self.n_groups - 1))
+            self._host = host
+        return self._host
+
+    def _record(self, i, g, tdcf=False):
+        """Polarity i's record of group g (None: pooled), checked; None for a group that lacks a class."""
+        rec = self.fetch()[i, 0 if g is None else 1 + g]
+        if g is not None and int(rec["n_nan"]) == 0 and (int(rec["n_tar"]) == 0 or int(rec["n_non"]) == 0):
+            return None
+        _check_record(rec, tdcf)
+        return rec
+
+    def eer(self, i=0, g=None):
+        rec = self._record(i, g)
+        if rec is None:
+            return None
+        frr, far, thr, _ = _rates(rec, "eer")
+        return float((frr + far) / 2.0), thr
+
+    def min_tdcf(self, i=0, g=None):
+        rec = self._record(i, g, tdcf=True)
+        if rec is None:
+            return None
+        C1, C2 = self.weights[0 if g is None else 1 + g]
+        frr, far, _, k = _rates(rec, "dcf")
+        return float((C1 * frr + C2 * far) / np.minimum(C1, C2)), k
+
+
+def eer_by_group_device(scores, labels, groups, n_groups, negate=False):
+    """compute_eer_by_group (of -scores with ``negate``) for fp32 scores and integer labels / groups on the GPU, up to
+    2^20 trials and ops.EVAL_MAX_GROUPS groups: one sort for all groups, enqueued on the current stream; ``.result()``
+    makes the one device-to-host copy and returns the list, bit-equal to the host's."""
+    m = DeviceGroupedMinima(scores, labels, groups, n_groups, (negate,))
+    return _Pending(m, lambda m: [m.eer(0, g) for g in range(m.n_groups)])
+
+
+def eer_both_polarities_by_group_device(scores, labels, groups, n_groups):
+    """eer_both_polarities_by_group on the GPU: both polarities enqueued back to back, one host copy in ``.result()``."""
+    def finish(m):
+        pairs = [(m.eer(0, g), m.eer(1, g)) for g in range(m.n_groups)]
+        return [None if p is None else min(p[0], q[0]) for p, q in pairs]
+    return _Pending(DeviceGroupedMinima(scores, labels, groups, n_groups, (False, True)), finish)
+
+
+def min_tdcf_by_group_device(scores, labels, groups, n_groups, rates_by_group, cost_model, negate=False):
+    """min_tdcf_by_group on the GPU: the host computes and checks each group's weights, the device finds the first
+    minimum of every group's curve; ``.result()`` -> [(min t-DCF, index) or None]."""
+    rates = _rates_of_group(rates_by_group, int(n_groups))
+    weights = [(1.0, 1.0)] + [tdcf_weights(*r, cost_model) for r in rates]  # (row 0: the pooled record, not read here)
+    m = DeviceGroupedMinima(scores, labels, groups, n_groups, (negate,), weights)
+    return _Pending(m, lambda m: [m.min_tdcf(0, g) for g in range(m.n_groups)])

@@ -1245,6 +1245,47 @@ def eval_det_min(scores, labels, record, ws, negate=False, c1=None, c2=None):
     return record
 
 
+EVAL_MAX_GROUPS = 128
+
+
+def eval_workspace_bytes_grouped(n, n_groups):
+    """Bytes of scratch eval_det_min_grouped needs for n trials in n_groups groups (ValueError beyond EVAL_MAX_TRIALS /
+    EVAL_MAX_GROUPS)."""
+    n, n_groups = int(n), int(n_groups)
+    if n < 1 or n > EVAL_MAX_TRIALS:
+        raise ValueError("device metrics take 1 .. %d trials, got %d" % (EVAL_MAX_TRIALS, n))
+    if n_groups < 1 or n_groups > EVAL_MAX_GROUPS:
+        raise ValueError("device metrics take 1 .. %d groups, got %d" % (EVAL_MAX_GROUPS, n_groups))
+    return int(_hip.lib().air_eval_workspace_bytes_grouped(ci(n), ci(n_groups)))
+
+
+def eval_det_min_grouped(scores, labels, groups, n_groups, records, ws, negate=False, c12=None):
+    """eval_det_min for the pooled trials and for each of ``n_groups`` groups from ONE sort: ``groups`` (int32 | int64,
+    (n,)) holds each trial's group, -1 = member of every group; ``records`` ((n_groups + 1) * EVAL_RECORD_WORDS int32)
+    gets the pooled record and one per group, each what eval_det_min writes for that subset alone.  ``c12``: fp64
+    (n_groups + 1, 2) GPU tensor of the t-DCF weights (C1, C2) per record, or None.  Ids outside -1 .. n_groups - 1
+    are counted into reserved[0] of the pooled record.  Enqueues only: nothing is allocated or synchronised."""
+    n = _eval_args(scores, labels, ws)  # (the grouped scratch holds the ungrouped one: checked again below)
+    if not torch.is_tensor(groups) or groups.dim() != 1 or groups.numel() != n:
+        raise ValueError("groups must be 1-d and as long as the scores")
+    if groups.dtype not in (torch.int32, torch.int64):
+        raise _hip.AirError("groups must be int32 or int64, got %s" % groups.dtype)
+    n_groups = int(n_groups)
+    need = eval_workspace_bytes_grouped(n, n_groups)
+    if ws.numel() < need:
+        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (eval_workspace_bytes_grouped)" % need)
+    if records.dtype != torch.int32 or records.numel() != (n_groups + 1) * EVAL_RECORD_WORDS:
+        raise ValueError("records must be %d int32 words" % ((n_groups + 1) * EVAL_RECORD_WORDS))
+    if c12 is not None and (c12.dtype != torch.float64 or c12.numel() != 2 * (n_groups + 1)):
+        raise ValueError("c12 must be fp64 of shape (%d, 2)" % (n_groups + 1))
+    _hip.check(_hip.lib().air_eval_det_min_grouped(
+        dptr(scores), dptr(labels, labels.dtype), ci(labels.element_size()), dptr(groups, groups.dtype),
+        ci(groups.element_size()), ci(n), ci(n_groups), ci(1 if negate else 0), ci(0 if c12 is None else 1),
+        dptr(c12, torch.float64, allow_none=True), dptr(records, torch.int32), dptr(ws, torch.uint8), csz(ws.numel()),
+        stream()), "air_eval_det_min_grouped")
+    return records
+
+
 def eval_sorted_keys(scores, labels, negate=False):
     """The n sorted composite keys ((ordered image of the score) << 1 | is_spoof) as an int64 GPU tensor, and the
     record with the class / NaN / inf counts - the first two steps of eval_det_min, for tests of the sort."""

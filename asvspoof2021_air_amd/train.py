@@ -36,7 +36,15 @@ def adjust_learning_rate(lr0, optimizer, epoch_num, lr_decay=0.5, interval=30):
 
 # what Trainer.evaluate returns: the monitored loss, the EER (min over both polarities), the min t-DCF (None without
 # ``tdcf``) and the pass's scores and labels, still on the device
-EvalResult = collections.namedtuple("EvalResult", ("loss", "eer", "min_tdcf", "scores", "labels"))
+class EvalResult(collections.namedtuple("EvalResult", ("loss", "eer", "min_tdcf", "scores", "labels"))):
+    """Five fields, as callers unpack it; ``by_group`` hangs off it as an attribute: None, or with
+    ``evaluate(n_groups=...)`` one GroupResult per group (None for a group without bona fide or without spoof trials)."""
+    by_group = None
+
+
+# one row of the breakdown: the group's name (its index without ``group_names``), the EER of (scores, -scores), and the
+# EER and min t-DCF (None without ``tdcf``) in the polarity that wins the POOLED EER - a system has one polarity
+GroupResult = collections.namedtuple("GroupResult", ("name", "eers", "eer", "min_tdcf"))
 
 ADD_LOSSES = (None, "isolate", "iso_sq", "ang_iso", "p2sgrad")
 # the head a given loss module stands for (any other module: the OC-Softmax head's interface, as before)
@@ -309,7 +317,7 @@ class Trainer:
         return self.loss(feats, labels)
 
     @torch.no_grad()
-    def evaluate(self, batches, epoch_num=None, log=None, capacity=None, tdcf=None):
+    def evaluate(self, batches, epoch_num=None, log=None, capacity=None, tdcf=None, n_groups=None, group_names=None):
         """The dev / eval half of the reference's epoch (main_train.py:484-668) over ``batches``, an iterable of
         ``(pcm, labels[, start[, lengths]])`` as eval_batch takes them, without a host synchronisation inside the
         loop: per batch eval_batch, the loss into a device vector, scores and labels into device buffers
@@ -322,16 +330,39 @@ class Trainer:
         "test_loss.log" - the line log_eval writes for ``epoch_num``.  Bit-equal to the per-batch loop
         (``eval_batch`` + ``.item()``, ``np.nanmean``, ``eval_metrics.eer_both_polarities``).  Up to 2^20 trials.
         world > 1: every rank evaluates what it is given; no collective runs.  Returns an EvalResult
-        (loss, eer, min_tdcf or None, the device score and label tensors)."""
+        (loss, eer, min_tdcf or None, the device score and label tensors).
+
+        ``n_groups=G``: the breakdown by attack or by channel condition.  A batch is then
+        ``(pcm, labels, start, lengths, groups)`` (``start`` / ``lengths`` may be None) with one integer group per trial,
+        0 .. G - 1 or -1 for "member of every group" (eval_metrics, "breakdown"); the groups go into a third device
+        buffer, both polarities are sorted once each for the pooled curve and all groups
+        (eval_metrics.DeviceGroupedMinima), and the records still come back with the losses in the one copy.  The
+        result's ``by_group`` is a list of GroupResult (``group_names``: G names for them), None where a group lacks a
+        class.  ``tdcf`` may carry a fifth element, one (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) per group; without it
+        every group takes the pooled rates.  Without ``n_groups`` nothing changes: same launches, ``by_group`` None."""
         from .devbuf import DeviceVector
-        from .eval_metrics import DeviceCurveMinima, tdcf_weights
-        from .ops import EVAL_RECORD_WORDS
+        from .eval_metrics import DeviceCurveMinima, DeviceGroupedMinima, _rates_of_group, tdcf_weights
+        from .ops import EVAL_MAX_GROUPS, EVAL_RECORD_WORDS
         if log not in (None, "dev_loss.log", "test_loss.log"):
             raise ValueError("log must be None, 'dev_loss.log' or 'test_loss.log', got %r" % (log,))
-        weights = tdcf_weights(*tdcf) if tdcf is not None else None  # (refused before the pass, not after it)
+        weights = tdcf_weights(*tdcf[:4]) if tdcf is not None else None  # (refused before the pass, not after it)
+        grouped = n_groups is not None
+        if not grouped and (group_names is not None or (tdcf is not None and len(tdcf) > 4)):
+            raise ValueError("group_names and per-group t-DCF rates need n_groups")
+        if grouped:
+            n_groups = int(n_groups)
+            if n_groups < 1 or n_groups > EVAL_MAX_GROUPS:
+                raise ValueError("n_groups must be 1 .. %d, got %d" % (EVAL_MAX_GROUPS, n_groups))
+            if group_names is not None and len(group_names) != n_groups:
+                raise ValueError("group_names must name %d groups, got %d" % (n_groups, len(group_names)))
+            if weights is not None:  # row 0: the pooled weights; per group its own rates, or the pooled ones
+                rates = _rates_of_group(tdcf[4] if len(tdcf) > 4 else tdcf[:3], n_groups)
+                weights = [weights] + [tdcf_weights(*r, tdcf[3]) for r in rates]
         n_batches = len(batches) if hasattr(batches, "__len__") else None
-        losses = scores = labs = None
+        losses = scores = labs = grps = None
         for batch in batches:
+            if grouped and len(batch) != 5:
+                raise ValueError("with n_groups a batch is (pcm, labels, start, lengths, groups), got %d items" % len(batch))
             pcm = batch[0]
             labels = batch[1].to(device=self.device, dtype=torch.int64, non_blocking=True).contiguous()
             loss, score = self.eval_batch(pcm, labels, batch[2] if len(batch) > 2 else None,
@@ -341,25 +372,43 @@ class Trainer:
                 losses = DeviceVector(torch.float32, self.device, n_batches or 64)
                 scores = DeviceVector(torch.float32, self.device, trials)
                 labs = DeviceVector(torch.int64, self.device, trials)
+                grps = DeviceVector(torch.int64, self.device, trials) if grouped else None
             losses.append(loss)
             scores.append(score)
             labs.append(labels)
+            if grouped:
+                grps.append(batch[4].to(device=self.device, dtype=torch.int64, non_blocking=True))
         if losses is None:
             raise ValueError("evaluate() needs at least one batch")
-        words = 2 * EVAL_RECORD_WORDS
+        if grouped and grps.n != scores.n:
+            raise ValueError("the batches gave %d groups for %d trials" % (grps.n, scores.n))
+        words = 2 * ((n_groups + 1) if grouped else 1) * EVAL_RECORD_WORDS
         pack = torch.empty(words + losses.n, dtype=torch.int32, device=self.device)  # [records | losses]: one fetch
-        minima = DeviceCurveMinima(scores.view(), labs.view(), (False, True), weights,
-                                   out=pack[:words].view(2, EVAL_RECORD_WORDS))
+        if grouped:
+            minima = DeviceGroupedMinima(scores.view(), labs.view(), grps.view(), n_groups, (False, True), weights,
+                                         out=pack[:words])
+        else:
+            minima = DeviceCurveMinima(scores.view(), labs.view(), (False, True), weights,
+                                       out=pack[:words].view(2, EVAL_RECORD_WORDS))
         pack[words:].view(torch.float32).copy_(losses.view())
         host = pack.cpu().numpy()
         minima.fetch(host[:words])
         batch_losses = host[words:].view(np.float32).astype(np.float64)  # what .item() per batch would have listed
         eers = (minima.eer(0)[0], minima.eer(1)[0])
         eer = min(eers)
-        min_tdcf = minima.min_tdcf(0 if eers[0] < eers[1] else 1)[0] if weights is not None else None
+        win = 0 if eers[0] < eers[1] else 1
+        min_tdcf = minima.min_tdcf(win)[0] if weights is not None else None
         if log is not None:
             self.log_eval(epoch_num, batch_losses, eer, name=log)
-        return EvalResult(float(np.nanmean(batch_losses)), eer, min_tdcf, scores.view(), labs.view())
+        out = EvalResult(float(np.nanmean(batch_losses)), eer, min_tdcf, scores.view(), labs.view())
+        if grouped:
+            out.by_group = []
+            for g in range(n_groups):
+                pair = (minima.eer(0, g), minima.eer(1, g))  # (a group lacks a class in both polarities or in neither)
+                out.by_group.append(None if pair[0] is None else GroupResult(
+                    g if group_names is None else group_names[g], (pair[0][0], pair[1][0]), pair[win][0],
+                    minima.min_tdcf(win, g)[0] if weights is not None else None))
+        return out
 
     def step(self, pcm, labels, start=None, lengths=None):
         """``lengths`` None: a batch of one length; a ``start`` forces the eager step.  ``lengths`` int32 (B,): a ragged

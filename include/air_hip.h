@@ -1042,6 +1042,37 @@ int air_eval_keys(const float* scores, const void* labels, int label_bytes, int 
 int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream);
 int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
                        air_stream_t stream);
+/* The breakdown of the same pass by attack or by channel condition: every trial also carries an integer group id
+ * (groups: n integers of group_bytes (4 | 8) bytes).  g in 0 .. n_groups-1: the trial belongs to group g; g == -1: the
+ * trial belongs to EVERY group (per-attack tables: bona fide trials -1, spoof trials their attack; per-channel tables:
+ * every trial its condition).  Any other id belongs to no group and is counted into recs[0].reserved[0]: the caller
+ * must refuse the result.  1 <= n_groups <= air_eval_max_groups() (128), otherwise AIR_EUNSUPPORTED.
+ *
+ * recs holds n_groups + 1 records.  recs[0] is the record air_eval_det_min writes for all n trials (apart from
+ * reserved[0]).  recs[1 + g] is, field for field, the record air_eval_det_min writes when it is given the trials of
+ * {i : g_i == g or g_i == -1} alone: n_tar, n_non, n_nan, n_inf, n_distinct of that subset, eer_idx / dcf_idx as the
+ * index on the subset's OWN curve (members rejected so far), *_rej_non the spoof members among them, *_score_first the
+ * subset's lowest score, *_score_at the score of its k-th lowest member.  A group without members has all-zero counts
+ * and 0.0 scores; a group with an empty class is the caller's to refuse, as for air_eval_det_min (its indices are
+ * meaningless).  The t-DCF weights are per record: c12_dev points to (n_groups + 1) x {c1, c2} doubles in
+ * DEVICE memory (row 0 pooled, row 1 + g group g; per-attack t-DCF has a C2 per attack) and is read only with
+ * want_dcf (NULL otherwise).
+ *
+ * One key per trial, built once and sorted ONCE per call whatever n_groups is: (score image << 9) | (is_spoof << 8) |
+ * code, code = g + 1 (0: every group, 255: none).  The group rides below the class bit, so "bona fide first among
+ * equal scores" holds inside every subset and the sort network is the one of air_eval_sort_keys.  Then per sort block a
+ * histogram of the codes (class counts, NaN / inf counts, last member), an exclusive prefix over the blocks per
+ * record, and the curve walk: per record the scan of "member and spoof" / "member and bona fide" over the sorted keys,
+ * fp64 frr / far from the subset's own counts at k = 0 and at every k whose trial k - 1 is a member, the first minimum
+ * of |frr - far| and of the normalised t-DCF, and the subset's distinct scores (a member counts when the member before
+ * it has another score).  No allocation, no host synchronisation, integer atomics only (counts and the index of a
+ * block's last member), fixed-order reductions; ws: air_eval_workspace_bytes_grouped(n, n_groups) bytes (0: out of
+ * range), 16-byte aligned. */
+int air_eval_max_groups(void);
+size_t air_eval_workspace_bytes_grouped(int n, int n_groups);
+int air_eval_det_min_grouped(const float* scores, const void* labels, int label_bytes, const void* groups,
+                             int group_bytes, int n, int n_groups, int negate, int want_dcf, const double* c12_dev,
+                             air_eval_record* recs, void* ws, size_t ws_bytes, air_stream_t stream);
 
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight

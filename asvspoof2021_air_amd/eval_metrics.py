@@ -265,51 +265,87 @@ def _check_record(rec, tdcf=False):
             raise ValueError("soft CM scores are needed, not binary decisions")
 
 
-class DeviceCurveMinima:
-    """The enqueued device metrics of one score set: one air_eval_record per polarity in ``records`` ((P, 16) int32 on
-    the GPU; the rows of ``out`` when the caller packs them with other results of a pass).  Nothing has been copied
-    or synchronised until ``fetch()`` / ``result()``."""
+class DeviceGroupedMinima:
+    """The enqueued device metrics of one score set, for the pooled trials and every group from one sort per polarity
+    (ops.eval_det_min_grouped): ``records`` is (P, n_groups + 1, 16) int32 on the GPU (``out`` when the caller packs it
+    with other results of a pass), row 0 of a polarity the pooled air_eval_record, row 1 + g group g's - what the chain
+    writes for that subset alone.  ``weights``: None or (n_groups + 1, 2) t-DCF weights (C1, C2) per record.  Without
+    groups (``groups`` None, ``n_groups`` 0: ops.eval_det_min, nothing uploaded) the axis of the groups is left out:
+    ``records`` (P, 16), ``fetch()`` (P,).  Nothing has been copied back or synchronised until ``fetch()`` /
+    ``result()``; ids outside -1 .. n_groups - 1 raise ValueError there."""
 
-    def __init__(self, scores, labels, negates, weights=None, out=None):
+    def __init__(self, scores, labels, groups, n_groups, negates, weights=None, out=None):
         import torch
         from . import ops
-        if not (torch.is_tensor(scores) and scores.is_cuda and torch.is_tensor(labels) and labels.is_cuda):
-            raise ValueError("the device metrics take GPU tensors (compute_eer is the host path)")
+        given = (scores, labels) if groups is None else (scores, labels, groups)
+        if not all(torch.is_tensor(t) and t.is_cuda for t in given):
+            raise ValueError("the device metrics take GPU tensors (compute_eer / compute_eer_by_group are the host path)")
         if scores.dtype != torch.float32:
             raise ValueError("scores must be fp32, got %s" % scores.dtype)
-        scores, labels = scores.reshape(-1).contiguous(), labels.reshape(-1).contiguous()
+        given = [t.reshape(-1).contiguous() for t in given]
+        self.n_groups = int(n_groups)
         self.negates = tuple(bool(n) for n in negates)
-        self.weights = weights
-        self.records = out if out is not None else torch.empty(len(self.negates), ops.EVAL_RECORD_WORDS, dtype=torch.int32,
-                                                               device=scores.device)
-        ws = torch.empty(ops.eval_workspace_bytes(scores.numel()), dtype=torch.uint8, device=scores.device)
-        c1, c2 = (None, None) if weights is None else (float(weights[0]), float(weights[1]))
-        for row, neg in zip(self.records, self.negates):  # back to back on the stream, sharing the scratch
-            ops.eval_det_min(scores, labels, row, ws, negate=neg, c1=c1, c2=c2)
+        self.weights = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(self.n_groups + 1, 2)
+        if groups is None:
+            self._shape = (len(self.negates),)
+            nbytes = ops.eval_workspace_bytes(given[0].numel())
+            c1, c2 = (None, None) if weights is None else (float(self.weights[0, 0]), float(self.weights[0, 1]))
+            run = lambda rows, neg: ops.eval_det_min(*given, rows, ws, negate=neg, c1=c1, c2=c2)
+        else:
+            self._shape = (len(self.negates), self.n_groups + 1)
+            nbytes = ops.eval_workspace_bytes_grouped(given[0].numel(), self.n_groups)
+            c12 = None if weights is None else torch.from_numpy(self.weights).to(scores.device)
+            run = lambda rows, neg: ops.eval_det_min_grouped(*given, self.n_groups, rows, ws, negate=neg, c12=c12)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=scores.device)
+        shape = self._shape + (ops.EVAL_RECORD_WORDS,)
+        self.records = out.view(shape) if out is not None else torch.empty(shape, dtype=torch.int32, device=scores.device)
+        for rows, neg in zip(self.records, self.negates):  # back to back on the stream, sharing the scratch
+            run(rows, neg)
         self._host = None
 
     def fetch(self, host_words=None):
         """The single device-to-host copy (or the caller's copy of the packed ``out``, as int32 words)."""
         if self._host is None:
             words = self.records.cpu().numpy() if host_words is None else np.asarray(host_words)
-            self._host = np.ascontiguousarray(words, dtype=np.int32).reshape(-1).view(_RECORD)
+            host = np.ascontiguousarray(words, dtype=np.int32).reshape(-1).view(_RECORD).reshape(self._shape)
+            bad = int(host[0, 0]["reserved"][0]) if host.ndim == 2 else 0
+            if bad:
+                raise ValueError("%d group ids lie outside -1 .. %d" % (bad, self.n_groups - 1))
+            self._host = host
         return self._host
 
-    def eer(self, i=0):
-        """(eer, threshold) of polarity i, finished on the host as compute_eer does."""
-        rec = self.fetch()[i]
-        _check_record(rec)
+    def _record(self, i, g, tdcf=False):
+        """Polarity i's record of group g (None: pooled), checked; None for a group that lacks a class."""
+        rec = self.fetch()[i] if len(self._shape) == 1 else self.fetch()[i, 0 if g is None else 1 + g]
+        if g is not None and int(rec["n_nan"]) == 0 and (int(rec["n_tar"]) == 0 or int(rec["n_non"]) == 0):
+            return None
+        _check_record(rec, tdcf)
+        return rec
+
+    def eer(self, i=0, g=None):
+        """(eer, threshold) of polarity i (of its group g), finished on the host as compute_eer does."""
+        rec = self._record(i, g)
+        if rec is None:
+            return None
         frr, far, thr, _ = _rates(rec, "eer")
         return float((frr + far) / 2.0), thr
 
-    def min_tdcf(self, i=0):
-        """(min t-DCF, index of the operating point) of polarity i: the device's argmin, the value recomputed from the
-        counts with the host formula of compute_tDCF."""
-        rec = self.fetch()[i]
-        _check_record(rec, tdcf=True)
-        C1, C2 = self.weights
+    def min_tdcf(self, i=0, g=None):
+        """(min t-DCF, index of the operating point) of polarity i (of its group g): the device's argmin, the value
+        recomputed from the counts with the host formula of compute_tDCF."""
+        rec = self._record(i, g, tdcf=True)
+        if rec is None:
+            return None
+        C1, C2 = self.weights[0 if g is None else 1 + g]
         frr, far, _, k = _rates(rec, "dcf")
         return float((C1 * frr + C2 * far) / np.minimum(C1, C2)), k
+
+
+class DeviceCurveMinima(DeviceGroupedMinima):
+    """DeviceGroupedMinima without groups: one air_eval_record per polarity; ``weights``: None or the pair (C1, C2)."""
+
+    def __init__(self, scores, labels, negates, weights=None, out=None):
+        super().__init__(scores, labels, None, 0, negates, weights, out)
 
 
 class _Pending:
@@ -344,67 +380,6 @@ def min_tdcf_device(scores, labels, Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_mo
 
 
 # ------------------------------------------------------------------ the breakdown on the device
-class DeviceGroupedMinima:
-    """DeviceCurveMinima for the pooled trials and every group from one sort per polarity (air_eval_det_min_grouped):
-    ``records`` is (P, n_groups + 1, 16) int32 on the GPU (``out`` when the caller packs it with other results), row 0
-    of a polarity the pooled record, row 1 + g group g's - what the ungrouped kernel writes for that subset alone.
-    ``weights``: None or (n_groups + 1, 2) t-DCF weights (C1, C2) per record.  Nothing has been copied back or
-    synchronised until ``fetch()`` / ``result()``; ids outside -1 .. n_groups - 1 raise ValueError there."""
-
-    def __init__(self, scores, labels, groups, n_groups, negates, weights=None, out=None):
-        import torch
-        from . import ops
-        if not all(torch.is_tensor(t) and t.is_cuda for t in (scores, labels, groups)):
-            raise ValueError("the device metrics take GPU tensors (compute_eer_by_group is the host path)")
-        if scores.dtype != torch.float32:
-            raise ValueError("scores must be fp32, got %s" % scores.dtype)
-        scores, labels, groups = (t.reshape(-1).contiguous() for t in (scores, labels, groups))
-        self.n_groups = int(n_groups)
-        self.negates = tuple(bool(n) for n in negates)
-        shape = (len(self.negates), self.n_groups + 1, ops.EVAL_RECORD_WORDS)
-        ws = torch.empty(ops.eval_workspace_bytes_grouped(scores.numel(), self.n_groups), dtype=torch.uint8, device=scores.device)
-        self.weights = None if weights is None else np.asarray(weights, dtype=np.float64).reshape(self.n_groups + 1, 2)
-        c12 = None if weights is None else torch.from_numpy(self.weights).to(scores.device)
-        self.records = out.view(shape) if out is not None else torch.empty(shape, dtype=torch.int32, device=scores.device)
-        for rows, neg in zip(self.records, self.negates):  # back to back on the stream, sharing the scratch
-            ops.eval_det_min_grouped(scores, labels, groups, self.n_groups, rows, ws, negate=neg, c12=c12)
-        self._host = None
-
-    def fetch(self, host_words=None):
-        """The single device-to-host copy (or the caller's copy of the packed ``out``, as int32 words)."""
-        if self._host is None:
-            words = self.records.cpu().numpy() if host_words is None else np.asarray(host_words)
-            host = np.ascontiguousarray(words, dtype=np.int32).reshape(-1).view(_RECORD).reshape(len(self.negates), self.n_groups + 1)
-            bad = int(host[0, 0]["reserved"][0])
-            if bad:
-                raise ValueError("%d group ids lie outside -1 .. %d" % (bad, self.n_groups - 1))
-            self._host = host
-        return self._host
-
-    def _record(self, i, g, tdcf=False):
-        """Polarity i's record of group g (None: pooled), checked; None for a group that lacks a class."""
-        rec = self.fetch()[i, 0 if g is None else 1 + g]
-        if g is not None and int(rec["n_nan"]) == 0 and (int(rec["n_tar"]) == 0 or int(rec["n_non"]) == 0):
-            return None
-        _check_record(rec, tdcf)
-        return rec
-
-    def eer(self, i=0, g=None):
-        rec = self._record(i, g)
-        if rec is None:
-            return None
-        frr, far, thr, _ = _rates(rec, "eer")
-        return float((frr + far) / 2.0), thr
-
-    def min_tdcf(self, i=0, g=None):
-        rec = self._record(i, g, tdcf=True)
-        if rec is None:
-            return None
-        C1, C2 = self.weights[0 if g is None else 1 + g]
-        frr, far, _, k = _rates(rec, "dcf")
-        return float((C1 * frr + C2 * far) / np.minimum(C1, C2)), k
-
-
 def eer_by_group_device(scores, labels, groups, n_groups, negate=False):
     """compute_eer_by_group (of -scores with ``negate``) for fp32 scores and integer labels / groups on the GPU, up to
     2^20 trials and ops.EVAL_MAX_GROUPS groups: one sort for all groups, enqueued on the current stream; ``.result()``

@@ -1204,18 +1204,31 @@ def softmax_rows(logits):
 
 # ---------------------------------------------------------------- evaluation metrics (csrc/eval_metrics.hip)
 EVAL_MAX_TRIALS = 1 << 20
+EVAL_MAX_GROUPS = 128
 EVAL_RECORD_WORDS = 16  # air_eval_record as int32 words
 
 
 def eval_workspace_bytes(n):
-    """Bytes of scratch the evaluation-metric calls need for n trials (ValueError beyond EVAL_MAX_TRIALS)."""
+    """Bytes of scratch the evaluation-metric calls without groups need for n trials (ValueError beyond
+    EVAL_MAX_TRIALS)."""
     n = int(n)
     if n < 1 or n > EVAL_MAX_TRIALS:
         raise ValueError("device metrics take 1 .. %d trials, got %d" % (EVAL_MAX_TRIALS, n))
     return int(_hip.lib().air_eval_workspace_bytes(ci(n)))
 
 
-def _eval_args(scores, labels, ws, record=None):
+def eval_workspace_bytes_grouped(n, n_groups):
+    """Bytes of scratch eval_det_min_grouped needs for n trials in n_groups groups (ValueError beyond EVAL_MAX_TRIALS /
+    EVAL_MAX_GROUPS)."""
+    n_groups = int(n_groups)
+    if n_groups < 1 or n_groups > EVAL_MAX_GROUPS:
+        raise ValueError("device metrics take 1 .. %d groups, got %d" % (EVAL_MAX_GROUPS, n_groups))
+    eval_workspace_bytes(n)  # (the range of n)
+    return int(_hip.lib().air_eval_workspace_bytes_grouped(ci(int(n)), ci(n_groups)))
+
+
+def _eval_args(scores, labels, ws, records=None, groups=None, n_groups=0):
+    """The checks of both eval_det_min calls: ``groups`` None and ``n_groups`` 0 for the one without groups."""
     if not (torch.is_tensor(scores) and torch.is_tensor(labels)):
         raise _hip.AirError("scores and labels must be GPU tensors (the HIP path has no CPU fallback)")
     if scores.dim() != 1 or labels.dim() != 1 or labels.numel() != scores.numel():
@@ -1224,11 +1237,18 @@ def _eval_args(scores, labels, ws, record=None):
     if labels.dtype not in (torch.int32, torch.int64):
         raise _hip.AirError("labels must be int32 or int64, got %s" % labels.dtype)
     n = scores.numel()
-    need = eval_workspace_bytes(n)
+    if groups is not None:
+        if not torch.is_tensor(groups) or groups.dim() != 1 or groups.numel() != n:
+            raise ValueError("groups must be 1-d and as long as the scores")
+        if groups.dtype not in (torch.int32, torch.int64):
+            raise _hip.AirError("groups must be int32 or int64, got %s" % groups.dtype)
+    need = eval_workspace_bytes(n) if groups is None else eval_workspace_bytes_grouped(n, n_groups)
     if ws.dtype != torch.uint8 or ws.numel() < need:
-        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (eval_workspace_bytes)" % need)
-    if record is not None and (record.dtype != torch.int32 or record.numel() != EVAL_RECORD_WORDS):
-        raise ValueError("record must be %d int32 words" % EVAL_RECORD_WORDS)
+        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (eval_workspace_bytes%s)" % (
+            need, "" if groups is None else "_grouped"))
+    words = (n_groups + 1) * EVAL_RECORD_WORDS
+    if records is not None and (records.dtype != torch.int32 or records.numel() != words):
+        raise ValueError("records must be %d int32 words" % words)
     return n
 
 
@@ -1245,37 +1265,16 @@ def eval_det_min(scores, labels, record, ws, negate=False, c1=None, c2=None):
     return record
 
 
-EVAL_MAX_GROUPS = 128
-
-
-def eval_workspace_bytes_grouped(n, n_groups):
-    """Bytes of scratch eval_det_min_grouped needs for n trials in n_groups groups (ValueError beyond EVAL_MAX_TRIALS /
-    EVAL_MAX_GROUPS)."""
-    n, n_groups = int(n), int(n_groups)
-    if n < 1 or n > EVAL_MAX_TRIALS:
-        raise ValueError("device metrics take 1 .. %d trials, got %d" % (EVAL_MAX_TRIALS, n))
-    if n_groups < 1 or n_groups > EVAL_MAX_GROUPS:
-        raise ValueError("device metrics take 1 .. %d groups, got %d" % (EVAL_MAX_GROUPS, n_groups))
-    return int(_hip.lib().air_eval_workspace_bytes_grouped(ci(n), ci(n_groups)))
-
-
 def eval_det_min_grouped(scores, labels, groups, n_groups, records, ws, negate=False, c12=None):
     """eval_det_min for the pooled trials and for each of ``n_groups`` groups from ONE sort: ``groups`` (int32 | int64,
     (n,)) holds each trial's group, -1 = member of every group; ``records`` ((n_groups + 1) * EVAL_RECORD_WORDS int32)
     gets the pooled record and one per group, each what eval_det_min writes for that subset alone.  ``c12``: fp64
     (n_groups + 1, 2) GPU tensor of the t-DCF weights (C1, C2) per record, or None.  Ids outside -1 .. n_groups - 1
     are counted into reserved[0] of the pooled record.  Enqueues only: nothing is allocated or synchronised."""
-    n = _eval_args(scores, labels, ws)  # (the grouped scratch holds the ungrouped one: checked again below)
-    if not torch.is_tensor(groups) or groups.dim() != 1 or groups.numel() != n:
+    if groups is None:
         raise ValueError("groups must be 1-d and as long as the scores")
-    if groups.dtype not in (torch.int32, torch.int64):
-        raise _hip.AirError("groups must be int32 or int64, got %s" % groups.dtype)
     n_groups = int(n_groups)
-    need = eval_workspace_bytes_grouped(n, n_groups)
-    if ws.numel() < need:
-        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (eval_workspace_bytes_grouped)" % need)
-    if records.dtype != torch.int32 or records.numel() != (n_groups + 1) * EVAL_RECORD_WORDS:
-        raise ValueError("records must be %d int32 words" % ((n_groups + 1) * EVAL_RECORD_WORDS))
+    n = _eval_args(scores, labels, ws, records, groups, n_groups)
     if c12 is not None and (c12.dtype != torch.float64 or c12.numel() != 2 * (n_groups + 1)):
         raise ValueError("c12 must be fp64 of shape (%d, 2)" % (n_groups + 1))
     _hip.check(_hip.lib().air_eval_det_min_grouped(
@@ -1287,17 +1286,15 @@ def eval_det_min_grouped(scores, labels, groups, n_groups, records, ws, negate=F
 
 
 def eval_sorted_keys(scores, labels, negate=False):
-    """The n sorted composite keys ((ordered image of the score) << 1 | is_spoof) as an int64 GPU tensor, and the
-    record with the class / NaN / inf counts - the first two steps of eval_det_min, for tests of the sort."""
+    """The n sorted composite keys ((ordered image of the score) << 9 | is_spoof << 8, no group code) as an int64 GPU
+    tensor - the first two steps of eval_det_min, for tests of the sort."""
     ws = torch.empty(eval_workspace_bytes(scores.numel()), dtype=torch.uint8, device=scores.device)
-    record = torch.empty(EVAL_RECORD_WORDS, dtype=torch.int32, device=scores.device)
-    n = _eval_args(scores, labels, ws, record)
+    n = _eval_args(scores, labels, ws)
     L = _hip.lib()
     _hip.check(L.air_eval_keys(dptr(scores), dptr(labels, labels.dtype), ci(labels.element_size()), ci(n),
-                               ci(1 if negate else 0), dptr(record, torch.int32), dptr(ws, torch.uint8), csz(ws.numel()),
-                               stream()), "air_eval_keys")
+                               ci(1 if negate else 0), dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_eval_keys")
     _hip.check(L.air_eval_sort_keys(ci(n), dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_eval_sort_keys")
-    return ws[:n * 8].view(torch.int64).clone(), record
+    return ws[:n * 8].view(torch.int64).clone()
 
 
 # BatchNorm's num_batches_tracked counters: one multi-tensor add per forward instead of one 4 us ATen launch per

@@ -324,7 +324,7 @@ class Trainer:
         (preallocated for ``capacity`` trials, or from ``len(batches)`` where it has one; grown by device-side copies
         otherwise).  Behind the loop the EER of both score polarities (main_train.py:662-664) and, with
         ``tdcf=(Pfa_asv, Pmiss_asv, Pmiss_spoof_asv, cost_model)``, the min t-DCF of the polarity with the lower
-        EER (evaluate_tDCF_asvspoof19.py:53-67) are found on the device (eval_metrics.DeviceCurveMinima) and fetched
+        EER (evaluate_tDCF_asvspoof19.py:53-67) are found on the device (eval_metrics.DeviceGroupedMinima) and fetched
         with the loss vector in ONE copy; the monitored loss is ``np.nanmean`` of the per-batch losses on the host
         (main_train.py:671 - a device mean would not reproduce numpy's summation order).  ``log``: "dev_loss.log" or
         "test_loss.log" - the line log_eval writes for ``epoch_num``.  Bit-equal to the per-batch loop
@@ -339,9 +339,10 @@ class Trainer:
         (eval_metrics.DeviceGroupedMinima), and the records still come back with the losses in the one copy.  The
         result's ``by_group`` is a list of GroupResult (``group_names``: G names for them), None where a group lacks a
         class.  ``tdcf`` may carry a fifth element, one (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) per group; without it
-        every group takes the pooled rates.  Without ``n_groups`` nothing changes: same launches, ``by_group`` None."""
+        every group takes the pooled rates.  Without ``n_groups`` the same kernel chain runs on the pooled record alone
+        (as many launches as the pass had before the breakdown, and nothing uploaded); ``by_group`` is None."""
         from .devbuf import DeviceVector
-        from .eval_metrics import DeviceCurveMinima, DeviceGroupedMinima, _rates_of_group, tdcf_weights
+        from .eval_metrics import DeviceGroupedMinima, _rates_of_group, tdcf_weights
         from .ops import EVAL_MAX_GROUPS, EVAL_RECORD_WORDS
         if log not in (None, "dev_loss.log", "test_loss.log"):
             raise ValueError("log must be None, 'dev_loss.log' or 'test_loss.log', got %r" % (log,))
@@ -382,14 +383,10 @@ class Trainer:
             raise ValueError("evaluate() needs at least one batch")
         if grouped and grps.n != scores.n:
             raise ValueError("the batches gave %d groups for %d trials" % (grps.n, scores.n))
-        words = 2 * ((n_groups + 1) if grouped else 1) * EVAL_RECORD_WORDS
+        words = 2 * ((n_groups or 0) + 1) * EVAL_RECORD_WORDS
         pack = torch.empty(words + losses.n, dtype=torch.int32, device=self.device)  # [records | losses]: one fetch
-        if grouped:
-            minima = DeviceGroupedMinima(scores.view(), labs.view(), grps.view(), n_groups, (False, True), weights,
-                                         out=pack[:words])
-        else:
-            minima = DeviceCurveMinima(scores.view(), labs.view(), (False, True), weights,
-                                       out=pack[:words].view(2, EVAL_RECORD_WORDS))
+        minima = DeviceGroupedMinima(scores.view(), labs.view(), grps.view() if grouped else None, n_groups or 0,
+                                     (False, True), weights, out=pack[:words])
         pack[words:].view(torch.float32).copy_(losses.view())
         host = pack.cpu().numpy()
         minima.fetch(host[:words])

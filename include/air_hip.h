@@ -1002,19 +1002,38 @@ int air_amsoftmax_fwd(const float* x, const float* centers, const int64_t* label
  * The two minima the reference reads off the DET curve of a dev / eval pass, exactly, without leaving the stream:
  * the EER point of compute_eer (eval_metrics.py:19-46: mergesort, cumsum, argmin |frr - far|; called on both score
  * polarities at main_train.py:662-664) and the min t-DCF point (the argmin of evaluate_tDCF_asvspoof19.py:58-59 over
- * the curve of compute_tDCF, eval_metrics.py:157-172).  scores: n fp32; labels: n integers of label_bytes (4 | 8)
- * bytes, 0 = bona fide, anything else = spoof; negate != 0 evaluates -scores.  n <= air_eval_max_trials() (2^20),
- * more: AIR_EUNSUPPORTED.  No allocation, no host synchronisation: all scratch is the caller's workspace of
- * air_eval_workspace_bytes(n) bytes (0: n out of range; 16-byte aligned), everything is enqueued on `stream`.
+ * the curve of compute_tDCF, eval_metrics.py:157-172) - for all trials and, from the same sort, for each group of a
+ * breakdown by attack or by channel condition.  scores: n fp32; labels: n integers of label_bytes (4 | 8) bytes,
+ * 0 = bona fide, anything else = spoof; negate != 0 evaluates -scores.  n <= air_eval_max_trials() (2^20), more:
+ * AIR_EUNSUPPORTED.  No allocation, no host synchronisation: all scratch is the caller's workspace (16-byte aligned),
+ * everything is enqueued on `stream`.
  *
- * Per trial one 64-bit key ((order-preserving image of the score) << 1 | is_spoof, -0.0 taken as +0.0), padded with
- * all-ones sentinels to a power of two >= air_eval_sort_block() and sorted ascending by a bitonic network; the
- * inclusive scan of the class bit gives rejected_non[k] (and rejected_tar[k] = k - rejected_non[k]) after the k lowest
- * trials, k = 0 .. n; in fp64, frr = rejected_tar / n_tar, far = (n_non - rejected_non) / n_non, and the record gets
- * the FIRST k that minimises |frr - far| and, with want_dcf, the FIRST k that minimises
- * (c1 * frr + c2 * far) / min(c1, c2) (c1, c2: the C1, C2 of eval_metrics.py:160-162, computed by the caller).
- * The caller finishes on the host from the integer counts; it must refuse n_nan > 0 (numpy sorts NaN last) and an
- * empty class (the indices are then meaningless). */
+ * Groups (air_eval_det_min_grouped): groups holds n integers of group_bytes (4 | 8) bytes.  g in 0 .. n_groups-1: the
+ * trial belongs to group g; g == -1: the trial belongs to EVERY group (per-attack tables: bona fide trials -1, spoof
+ * trials their attack; per-channel tables: every trial its condition).  Any other id belongs to no group and is
+ * counted into recs[0].reserved[0]: the caller must refuse the result.  1 <= n_groups <= air_eval_max_groups() (128),
+ * otherwise AIR_EUNSUPPORTED.  air_eval_det_min is the same chain without groups: one record, reserved[0] = 0.
+ *
+ * Per trial one 64-bit key, (order-preserving image of the score) << 9 | is_spoof << 8 | code with -0.0 taken as +0.0
+ * and code = g + 1 (0: every group - every trial of a call without groups; 255: none).  The keys are padded with
+ * all-ones sentinels to a power of two >= air_eval_sort_block() and sorted ascending by a bitonic network, ONCE per
+ * call whatever n_groups is: the group rides below the class bit, so "bona fide first among equal scores" holds inside
+ * every subset.  Then per sort block the class / NaN / inf counts of every record (a histogram of the codes), an
+ * exclusive prefix over the blocks per record, and the curve walk: per record the scan of "member and spoof" / "member
+ * and bona fide" over the sorted keys gives rejected_non[k] and rejected_tar[k] after the record's k lowest members,
+ * k = 0 .. its size; in fp64, frr = rejected_tar / n_tar, far = (n_non - rejected_non) / n_non from the record's own
+ * counts, and the record gets the FIRST k that minimises |frr - far| and, with want_dcf, the FIRST k that minimises
+ * (c1 * frr + c2 * far) / min(c1, c2) (c1, c2: the C1, C2 of eval_metrics.py:160-162, computed by the caller), and its
+ * distinct scores (a member counts when the member before it has another score).  Integer atomics only (counts and
+ * the index of a block's last member), fixed-order reductions; every word of a record is written by the call.
+ *
+ * recs holds n_groups + 1 records.  recs[0] is the pooled record: every trial is a member.  recs[1 + g] is, field for
+ * field, the record the chain writes when it is given the trials of {i : g_i == g or g_i == -1} alone: n_tar, n_non,
+ * n_nan, n_inf, n_distinct of that subset, eer_idx / dcf_idx as the index on the subset's OWN curve (members rejected
+ * so far), *_rej_non the spoof members among them, *_score_first the subset's lowest score, *_score_at the score of its
+ * k-th lowest member.  A group without members has all-zero counts and 0.0 scores.  The caller finishes on the host
+ * from the integer counts; it must refuse n_nan > 0 (numpy sorts NaN last) and an empty class (the indices are then
+ * meaningless). */
 typedef struct air_eval_record {
   uint32_t n_tar, n_non;          /* bona fide / spoof trials */
   uint32_t n_nan, n_inf;          /* NaN / +-inf scores (compute_tDCF refuses both, eval_metrics.py:147-149) */
@@ -1029,50 +1048,27 @@ typedef struct air_eval_record {
 } air_eval_record; /* 64 bytes */
 int air_eval_max_trials(void);
 int air_eval_sort_block(void); /* keys sorted per workgroup in LDS: the block boundary of the network */
+int air_eval_max_groups(void);
+/* Workspace bytes without groups and with 1 .. air_eval_max_groups() of them; 0: an argument out of range. */
 size_t air_eval_workspace_bytes(int n);
-/* The whole chain: keys, sort, curve minima.  c1, c2 are read only with want_dcf. */
+size_t air_eval_workspace_bytes_grouped(int n, int n_groups);
+/* The whole chain, pooled: keys, sort, curve minima into one record.  c1, c2 are read only with want_dcf. */
 int air_eval_det_min(const float* scores, const void* labels, int label_bytes, int n, int negate, int want_dcf,
                      double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes, air_stream_t stream);
-/* Its three steps on the same workspace (the keys are its first npad * 8 bytes): air_eval_keys zeroes the record,
- * builds the padded keys and counts n_tar / n_non / n_nan / n_inf; air_eval_sort_keys sorts them (np.sort of the keys,
- * eval_metrics.py:26 up to the order of equal keys); air_eval_curve_min needs the record and the sorted keys of the
- * first two. */
-int air_eval_keys(const float* scores, const void* labels, int label_bytes, int n, int negate, air_eval_record* rec,
-                  void* ws, size_t ws_bytes, air_stream_t stream);
-int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream);
-int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
-                       air_stream_t stream);
-/* The breakdown of the same pass by attack or by channel condition: every trial also carries an integer group id
- * (groups: n integers of group_bytes (4 | 8) bytes).  g in 0 .. n_groups-1: the trial belongs to group g; g == -1: the
- * trial belongs to EVERY group (per-attack tables: bona fide trials -1, spoof trials their attack; per-channel tables:
- * every trial its condition).  Any other id belongs to no group and is counted into recs[0].reserved[0]: the caller
- * must refuse the result.  1 <= n_groups <= air_eval_max_groups() (128), otherwise AIR_EUNSUPPORTED.
- *
- * recs holds n_groups + 1 records.  recs[0] is the record air_eval_det_min writes for all n trials (apart from
- * reserved[0]).  recs[1 + g] is, field for field, the record air_eval_det_min writes when it is given the trials of
- * {i : g_i == g or g_i == -1} alone: n_tar, n_non, n_nan, n_inf, n_distinct of that subset, eer_idx / dcf_idx as the
- * index on the subset's OWN curve (members rejected so far), *_rej_non the spoof members among them, *_score_first the
- * subset's lowest score, *_score_at the score of its k-th lowest member.  A group without members has all-zero counts
- * and 0.0 scores; a group with an empty class is the caller's to refuse, as for air_eval_det_min (its indices are
- * meaningless).  The t-DCF weights are per record: c12_dev points to (n_groups + 1) x {c1, c2} doubles in
- * DEVICE memory (row 0 pooled, row 1 + g group g; per-attack t-DCF has a C2 per attack) and is read only with
- * want_dcf (NULL otherwise).
- *
- * One key per trial, built once and sorted ONCE per call whatever n_groups is: (score image << 9) | (is_spoof << 8) |
- * code, code = g + 1 (0: every group, 255: none).  The group rides below the class bit, so "bona fide first among
- * equal scores" holds inside every subset and the sort network is the one of air_eval_sort_keys.  Then per sort block a
- * histogram of the codes (class counts, NaN / inf counts, last member), an exclusive prefix over the blocks per
- * record, and the curve walk: per record the scan of "member and spoof" / "member and bona fide" over the sorted keys,
- * fp64 frr / far from the subset's own counts at k = 0 and at every k whose trial k - 1 is a member, the first minimum
- * of |frr - far| and of the normalised t-DCF, and the subset's distinct scores (a member counts when the member before
- * it has another score).  No allocation, no host synchronisation, integer atomics only (counts and the index of a
- * block's last member), fixed-order reductions; ws: air_eval_workspace_bytes_grouped(n, n_groups) bytes (0: out of
- * range), 16-byte aligned. */
-int air_eval_max_groups(void);
-size_t air_eval_workspace_bytes_grouped(int n, int n_groups);
+/* The whole chain with groups.  The t-DCF weights are per record: c12_dev points to (n_groups + 1) x {c1, c2} doubles
+ * in DEVICE memory (row 0 pooled, row 1 + g group g; per-attack t-DCF has a C2 per attack) and is read only with
+ * want_dcf (NULL otherwise). */
 int air_eval_det_min_grouped(const float* scores, const void* labels, int label_bytes, const void* groups,
                              int group_bytes, int n, int n_groups, int negate, int want_dcf, const double* c12_dev,
                              air_eval_record* recs, void* ws, size_t ws_bytes, air_stream_t stream);
+/* The three steps of air_eval_det_min on the same workspace (the keys are its first npad * 8 bytes): air_eval_keys
+ * builds the padded keys; air_eval_sort_keys sorts them (np.sort of the keys, eval_metrics.py:26 up to the order of
+ * equal keys); air_eval_curve_min needs only the sorted keys and writes the whole record. */
+int air_eval_keys(const float* scores, const void* labels, int label_bytes, int n, int negate, void* ws, size_t ws_bytes,
+                  air_stream_t stream);
+int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
+                       air_stream_t stream);
 
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight

@@ -118,7 +118,7 @@ def test_eer_equals_host_at_the_limit(kind, mix):
 
 @pytest.mark.parametrize("n", [1, 2, 4095, 4096, 4097, 8193, 71237])
 def test_sorted_keys_equal_numpy_sort(n):
-    """The sort alone: the device's keys are np.sort of the host's keys, and the record counts the classes."""
+    """The sort alone: the device's keys are np.sort of the host's keys; the whole chain's record counts the classes."""
     from asvspoof2021_air_amd import ops
     rng = np.random.default_rng(n)
     lab = rng.integers(0, 2, n).astype(np.int64) * rng.integers(1, 9, n)  # any nonzero label is a spoof
@@ -126,12 +126,15 @@ def test_sorted_keys_equal_numpy_sort(n):
     s[::7] = -0.0
     for negate in (False, True):
         for ldt in (torch.int64, torch.int32):
-            keys, rec = ops.eval_sorted_keys(torch.from_numpy(s).cuda(), torch.from_numpy(lab).cuda().to(ldt), negate=negate)
+            ds, dl = torch.from_numpy(s).cuda(), torch.from_numpy(lab).cuda().to(ldt)
+            keys = ops.eval_sorted_keys(ds, dl, negate=negate)
             v = (-s if negate else s) + np.float32(0.0)  # -0.0 -> +0.0
             u = v.view(np.uint32).astype(np.uint64)
             o = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
-            want = np.sort((o << np.uint64(1)) | (lab != 0).astype(np.uint64))
+            want = np.sort((o << np.uint64(9)) | ((lab != 0).astype(np.uint64) << np.uint64(8)))
             assert np.array_equal(keys.cpu().numpy().view(np.uint64), want), (n, negate, ldt)
+            rec = torch.empty(ops.EVAL_RECORD_WORDS, dtype=torch.int32, device="cuda")
+            ops.eval_det_min(ds, dl, rec, torch.empty(ops.eval_workspace_bytes(n), dtype=torch.uint8, device="cuda"), negate=negate)
             assert rec.cpu().numpy().view(np.uint32)[:4].tolist() == [int((lab == 0).sum()), int((lab != 0).sum()), 0, 0]
 
 

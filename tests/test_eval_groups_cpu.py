@@ -1,10 +1,12 @@
 """CPU: the breakdown of EER / min t-DCF by group (eval_metrics.compute_eer_by_group and friends) against a brute-force
 loop over the subsets, and a numpy model of the device's walk (one sort of keys that carry the group below the class
-bit, a masked scan per group: csrc/eval_metrics.hip, "grouped form") pinned to the same subset functions with ``==``."""
+bit, a masked scan per group: eval_walk_oracle.walk_model) pinned to the same subset functions with ``==``."""
 import numpy as np
 import pytest
 
 from asvspoof2021_air_amd import eval_metrics as em
+from eval_walk_oracle import (WALK_ASV, WALK_GROUPS, WALK_KINDS, WALK_SIZES, finish_eer, walk_case, walk_model, walk_rates,
+                              walk_weights)
 
 RATES = (0.05, 0.03, 0.4)
 
@@ -43,51 +45,6 @@ def brute_force(s, lab, grp, n_groups, rates=None, only=None):
             curve, _ = em.compute_tDCF(tar, non, *rates[g], em.asvspoof19_cost_model())
             out.append((float(curve[np.argmin(curve)]), int(np.argmin(curve))))
     return out
-
-
-def walk_model(s, lab, grp, n_groups, negate=False, weights=None):
-    """The device's formulation in numpy: records[1 + g] of air_eval_det_min_grouped (record 0: pooled)."""
-    v = (-s if negate else s) + np.float32(0.0)  # -0.0 -> +0.0
-    u = v.view(np.uint32).astype(np.uint64)
-    img = np.where(u & 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
-    code = np.where((grp >= -1) & (grp < n_groups), grp + 1, 255).astype(np.uint64)
-    keys = np.sort((img << np.uint64(9)) | ((lab != 0).astype(np.uint64) << np.uint64(8)) | code)
-    k_img, k_spoof, k_code = keys >> np.uint64(9), ((keys >> np.uint64(8)) & np.uint64(1)).astype(np.int64), keys & np.uint64(255)
-    bits = np.where(k_img & 0x80000000, k_img ^ 0x80000000, ~k_img & 0xFFFFFFFF).astype(np.uint32)
-    sorted_scores = bits.view(np.float32)
-    recs = np.zeros(n_groups + 1, dtype=em._RECORD)
-    recs[0]["reserved"][0] = int((code == 255).sum())
-    for r in range(n_groups + 1):
-        member = np.ones(keys.size, bool) if r == 0 else (k_code == 0) | (k_code == r)
-        at = np.flatnonzero(member)  # sorted position of the subset's k-th member, k = 1 ..
-        rn = np.cumsum(k_spoof[at])
-        rt = np.arange(1, at.size + 1) - rn
-        rec = recs[r]
-        rec["n_non"], rec["n_tar"] = int(k_spoof[at].sum()), int(at.size - k_spoof[at].sum())
-        rec["n_inf"] = int(np.isinf(sorted_scores[at]).sum())
-        rec["n_distinct"] = int(np.unique(k_img[at]).size)
-        if at.size == 0 or rec["n_tar"] == 0 or rec["n_non"] == 0:
-            continue
-        n_tar, n_non = np.float64(rec["n_tar"]), np.float64(rec["n_non"])
-        frr = np.concatenate(([0.0], rt / n_tar))
-        far = np.concatenate(([1.0], (int(rec["n_non"]) - rn) / n_non))
-        for which, curve in (("eer", np.abs(frr - far)),
-                             ("dcf", None if weights is None else (weights[r][0] * frr + weights[r][1] * far) / min(weights[r]))):
-            if curve is None:
-                continue
-            k = int(np.argmin(curve))  # the first minimum
-            rec[which + "_idx"], rec[which + "_rej_non"] = k, 0 if k == 0 else int(rn[k - 1])
-            rec[which + "_score_first"] = sorted_scores[at[0]]
-            rec[which + "_score_at"] = sorted_scores[at[max(k, 1) - 1]]
-        rec["has_dcf"] = 0 if weights is None else 1
-    return recs
-
-
-def finish_eer(rec):
-    if int(rec["n_tar"]) == 0 or int(rec["n_non"]) == 0:
-        return None
-    frr, far, thr, _ = em._rates(rec, "eer")
-    return float((frr + far) / 2.0), thr
 
 
 @pytest.mark.parametrize("mode", ["partition", "attack"])
@@ -193,6 +150,30 @@ def test_the_walk_model_counts_ids_out_of_range():
     s, lab, grp = make_case("random", 90, 4, "partition", 2)
     grp[[3, 50, 51]] = (-2, 4, 1 << 33)
     assert int(walk_model(s, lab, grp, 4)[0]["reserved"][0]) == 3
+
+
+@pytest.mark.parametrize("n", WALK_SIZES)
+def test_the_walk_model_without_groups_equals_the_pooled_host_functions(n):
+    """The numpy side of test_eval_walk_gpu.py on that test's own inputs: at n_groups = 0 the model's one record finishes
+    to compute_eer's pair, and its t-DCF point is the first minimum of compute_tDCF's curve at the same weights (where
+    compute_tDCF takes the scores: three distinct ones)."""
+    cost = em.asvspoof19_cost_model()
+    assert WALK_GROUPS[0] == 0
+    (c1, c2), = walk_weights(0)
+    for j, kind in enumerate(WALK_KINDS):
+        s, lab, grp = walk_case(n, 0, kind, 10 * n + j)
+        assert (grp == -1).all() and not np.isnan(s).any() and not np.isinf(s).any()
+        for negate in (False, True):
+            h = (-s if negate else s).astype(np.float64)
+            rec, = walk_model(s, lab, grp, 0, negate, walk_weights(0))
+            both = (lab == 0).any() and (lab != 0).any()
+            assert both == (n >= 2)
+            assert finish_eer(rec) == (em.compute_eer(h[lab == 0], h[lab != 0]) if both else None), (n, kind, negate)
+            assert int(rec["n_distinct"]) == np.unique(h).size and int(rec["reserved"][0]) == 0
+            if both and np.unique(h).size >= 3:
+                curve, _ = em.compute_tDCF(h[lab == 0], h[lab != 0], *WALK_ASV, walk_rates(0)[0][2], cost)
+                frr, far, _, k = em._rates(rec, "dcf")
+                assert (float((c1 * frr + c2 * far) / np.minimum(c1, c2)), k) == (float(curve[np.argmin(curve)]), int(np.argmin(curve)))
 
 
 # ------------------------------------------------------------------ score files

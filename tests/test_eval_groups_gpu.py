@@ -277,7 +277,7 @@ def test_the_groups_share_one_sort():
     plain, _ = sort_launches(lambda: em.compute_eer_device(ds, dl))
     grouped, names = sort_launches(lambda: em.eer_by_group_device(ds, dl, dg, G))
     assert plain > 0 and grouped == plain, (plain, grouped)
-    assert any("ev_gcurve_kernel" in k for k in names)
+    assert any("ev_curve_kernel" in k for k in names)
 
 
 # ------------------------------------------------------------------ Trainer.evaluate(n_groups=...)

@@ -8,7 +8,8 @@
     ``<idx>_<filename>_<tag>_<label>[_<channel>[_<device>]].pt`` under ``<path>/<part>/<feature>/``
     (preprocess.py:85, :156, :243; read at dataset.py:56-61, :144-159) - a drop-in for a user who already has them;
   * raw PCM (``PCMSource``: any list of waveforms; ``SyntheticSource``: the separable synthetic corpus of synth.py),
-    whose features come from the fused HIP LFCC (+ pad / chop) kernel instead of a ``.pt`` file.  Per item that is a
+    whose features come from the fused HIP LFCC (+ pad / chop) kernel - or, with ``feature="STFT"`` / ``"Melspec"``, from
+    the spectrogram kernels: items (1, feat_len, 257) / (1, feat_len, 128) - instead of a ``.pt`` file.  Per item that is a
     batch-1 launch (what preprocess.py:239-244 does); with ``return_pcm=True`` the item carries the waveform and
     ``collate_fn`` runs ONE fused LFCC -> pad/chop launch for the batch.  ``return_pcm='batch'`` / ``'ragged'`` hand the
     waveforms themselves to the trainer as one pinned host tensor (one length per batch / any lengths + ``lengths`` and
@@ -30,7 +31,7 @@ from torch.utils.data import Dataset
 from torch.utils.data.dataloader import default_collate
 
 from . import _hip
-from .feature_extraction import LFCC, pad_mode_id
+from .feature_extraction import LFCC, STFT, Melspec, pad_mode_id
 
 
 def pad_transpose(feat, feat_len=750, start=None, padding="repeat", silence_row=None):
@@ -156,18 +157,20 @@ class PCMSource:
                                "main_train.py:63) or DataLoader(..., multiprocessing_context='spawn')" % (what, self.device))
 
     def feature(self, i, ds):
-        """Features of one utterance on the GPU (preprocess.py:239-244 runs batch 1 too): with ``ds.pad_chop`` the
-        fused LFCC -> pad / chop kernel's (1, 60, feat_len) output viewed as (1, feat_len, 60), the crop offset drawn
-        like dataset.py:69; otherwise the plain (1, T, 60) LFCC."""
+        """Features of one utterance on the GPU (preprocess.py:239-244 runs batch 1 too), from the front-end that
+        ``ds.feature`` names (D = 60 LFCC, 257 STFT, 128 Melspec): with ``ds.pad_chop`` the fused front-end -> pad / chop
+        kernel's (1, D, feat_len) output viewed as (1, feat_len, D), the crop offset drawn like dataset.py:69; otherwise
+        the plain (1, T, D) features."""
         self._need_gpu_here("PCMSource.feature")
         pcm = self.pcm(i).to(self.device, non_blocking=True).unsqueeze(0)
+        fe = ds.frontend  # by ds.feature: LFCC (1, T, 60), STFT (1, T, 257), Melspec (1, T, 128) - dataset.py:62-65
         if not ds.pad_chop:
-            return ds.lfcc(pcm)
-        T = 1 + pcm.shape[1] // ds.lfcc.fs
+            return getattr(fe, "forward_frames", fe)(pcm)
+        T = 1 + pcm.shape[1] // fe.fs
         start = None
         if T > ds.feat_len:
             start = torch.tensor([np.random.randint(T - ds.feat_len)], dtype=torch.int32).to(self.device)
-        return ds.lfcc.forward_padded(pcm, ds.feat_len, start, ds.padding).transpose(1, 2)
+        return fe.forward_padded(pcm, ds.feat_len, start, ds.padding).transpose(1, 2)
 
 
 class SyntheticSource(PCMSource):
@@ -237,6 +240,7 @@ class _SpoofDataset(Dataset):
         # to a multiple of 16000 - every new capacity re-captures a replayed step, so give a fixed one for training
         self.ragged_samples = None
         self._lfcc = None
+        self._frontend = None
         self._silence_cpu = None
         if padding == "silence" and pad_chop and torch.cuda.is_available():
             self.prepare()
@@ -248,6 +252,35 @@ class _SpoofDataset(Dataset):
             self._lfcc = LFCC(320, 160, 512, 16000, 20, with_energy=False)
             self._lfcc.mutate_input = False
         return self._lfcc
+
+    PCM_FEATURES = ("LFCC", "STFT", "Melspec")  # the reference's three front-ends (feature_extraction.py:61-176)
+
+    @property
+    def frontend(self):
+        """The front-end a PCM source runs, chosen by ``feature``: the LFCC of dataset.py:13, STFT(320, 160, 512, 16000)
+        (preprocess.py:40) or Melspec() (preprocess.py:247-258).  Anything else has no kernel: ValueError."""
+        if self._frontend is None:
+            if self.feature == "LFCC":
+                self._frontend = self.lfcc
+            elif self.feature == "STFT":
+                self._frontend = STFT(320, 160, 512, 16000)
+                self._frontend.mutate_input = False
+            elif self.feature == "Melspec":
+                self._frontend = Melspec()
+            else:
+                raise ValueError("feature=%r over a PCM source: the HIP front-ends are %s (file sources read any folder)"
+                                 % (self.feature, ", ".join(self.PCM_FEATURES)))
+        return self._frontend
+
+    def _check_feature(self):
+        """A PCM source computes its features here: refuse at construction what no front-end makes."""
+        if not any(isinstance(s, PCMSource) for s in self._sources()):
+            return
+        if self.feature not in self.PCM_FEATURES:
+            self.frontend  # raises
+        if self.feature != "LFCC" and self.pad_chop and self.padding == "silence":
+            raise NotImplementedError("padding='silence' prepends an LFCC frame (dataset.py:13-16): feature=%r over a PCM "
+                                      "source pads with 'repeat' or 'zero'" % self.feature)
 
     # -- sources: [original] or [original, augmented]
     def _sources(self):
@@ -392,7 +425,8 @@ class _SpoofDataset(Dataset):
         next(s for s in self._sources() if isinstance(s, PCMSource))._need_gpu_here("collate_fn(return_pcm=True)")
         dev = next(s.device for s in self._sources() if isinstance(s, PCMSource))
         B = len(samples)
-        out = torch.empty((B, self.lfcc.out_dim, self.feat_len), device=dev, dtype=torch.float32)
+        fe = self.frontend
+        out = torch.empty((B, fe.out_dim, self.feat_len), device=dev, dtype=torch.float32)
         by_len = {}
         for j, smp in enumerate(samples):
             by_len.setdefault(int(smp[0].shape[0]), []).append(j)
@@ -400,7 +434,7 @@ class _SpoofDataset(Dataset):
         # would have made (dataset.py:69)
         starts = {}
         for j, smp in enumerate(samples):
-            T = 1 + int(smp[0].shape[0]) // self.lfcc.fs
+            T = 1 + int(smp[0].shape[0]) // fe.fs
             if T > self.feat_len:
                 starts[j] = np.random.randint(T - self.feat_len)
         for L, js in by_len.items():
@@ -408,7 +442,7 @@ class _SpoofDataset(Dataset):
             st = None
             if js[0] in starts:
                 st = torch.tensor([starts[j] for j in js], dtype=torch.int32).to(dev)
-            got = self.lfcc.forward_padded(pcm, self.feat_len, st, self.padding)
+            got = fe.forward_padded(pcm, self.feat_len, st, self.padding)
             if len(by_len) == 1:
                 out = got
             else:
@@ -451,7 +485,7 @@ class _SpoofDataset(Dataset):
             dst[j, n:] = 0
         start = np.zeros(len(samples), dtype=np.int32)
         for j, n in enumerate(lens):
-            T = 1 + n // self.lfcc.fs
+            T = 1 + n // self.frontend.fs
             if T > self.feat_len:
                 start[j] = np.random.randint(T - self.feat_len)
         return [pcm, torch.tensor(lens, dtype=torch.int32), torch.from_numpy(start)] + default_collate(
@@ -476,6 +510,7 @@ class ASVspoof2019(_SpoofDataset):
         else:
             raise ValueError("Access type should be LA or PA!")
         self.source = source if source is not None else FileSource(os.path.join(self.ptf, feature))
+        self._check_feature()
         if genuine_only:
             assert access_type == "LA"
             if part in ("train", "dev"):  # the bona fide files sort first (tag "-"): the first N (dataset.py:42-44)
@@ -514,6 +549,7 @@ class _AugDataset(_SpoofDataset):
         self._init_common(feature, feat_len, pad_chop, padding, return_pcm)
         self.ori_source = ori_source if ori_source is not None else FileSource(os.path.join(self.ori, feature))
         self.aug_source = aug_source if aug_source is not None else FileSource(os.path.join(self.ptf, feature))
+        self._check_feature()
         self.tag = dict(TAG_AUG)
         self.channel = list(self.CHANNELS)
         self.channel_dict = dict(zip(self.channel, range(len(self.channel))))
@@ -570,6 +606,7 @@ class ASVspoof2021LAeval(_SpoofDataset):
         self.path_to_features = self.ptf = path_to_features
         self._init_common(feature, feat_len, pad_chop, padding, return_pcm)
         self.source = source if source is not None else FileSource(os.path.join(path_to_features, feature))
+        self._check_feature()
 
     @property
     def all_files(self):

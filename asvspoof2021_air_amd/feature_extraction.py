@@ -1,4 +1,5 @@
-"""Drop-in for the reference's ``feature_extraction.LFCC`` (feature_extraction.py:61-138).
+"""Drop-ins for the reference's front-ends: ``LFCC`` (feature_extraction.py:61-138) and, at the end of this file,
+``STFT`` (:141-165) and ``Melspec`` (:168-176) on the kernels of csrc/spectral.hip.
 
 Same constructor, same ``forward(x:(B,L)) -> (B, 1+L//fs, 3*filter_num)``,
 same ``state_dict`` keys (``lfcc_fb``, ``l_dct.weight``), same in-place
@@ -243,10 +244,186 @@ class LFCC(nn.Module):
         return out
 
     def _preemph_inplace(self, x):
-        lib = _hip.lib()
+        preemph_inplace_(x)
+
+
+def preemph_inplace_(x):
+    """x[:, 1:] -= 0.97 * x[:, :-1] on the original samples, in place (feature_extraction.py:106, :157)."""
+    lib = _hip.lib()
+    B, L = x.shape
+    nbytes = lib.air_preemph_ws_bytes(_hip.ci(B), _hip.ci(L))
+    ws = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
+    _hip.check(lib.air_preemph_inplace(_hip.dptr(x), _hip.ci(B), _hip.ci(L), _hip.cf(0.97),
+                                       _hip.dptr(ws), _hip.csz(nbytes), _hip.stream()),
+               "air_preemph_inplace")
+
+
+class _Spectral(nn.Module):
+    """What the two spectrogram front-ends share (csrc/spectral.hip, ``air_spec_*``): the plan blob, the checks of
+    ``LFCC`` and its three entry points.  ``KIND`` / ``out_dim`` / ``fs`` (the hop) / ``NAME`` come from the subclass."""
+    KIND, NAME = 0, "?"
+
+    def __init__(self):
+        super().__init__()
+        self._plan = None
+        self._plan_key = None
+
+    def _flags(self):
+        return 0
+
+    def plan(self, device):
+        """Device-resident plan blob (window, twiddles, banded mel filterbank)."""
+        key = str(device)
+        if self._plan is None or self._plan_key != key:
+            L = _hip.lib()
+            host = torch.zeros(L.air_spec_plan_bytes(), dtype=torch.uint8)
+            _hip.check(L.air_spec_plan_build(_hip.ci(self.KIND), _hip.hptr(host, torch.uint8)), "air_spec_plan_build")
+            self._plan = host.to(device)
+            self._plan_key = key
+        return self._plan
+
+    def _check(self, x, padding=None):
+        if padding is not None and pad_mode_id(padding) == 2:
+            raise NotImplementedError("padding='silence' prepends an LFCC frame (dataset.py:13-16) and is served by LFCC "
+                                      "only; %s pads with 'repeat' or 'zero'" % self.NAME)
+        if x.dim() != 2:
+            raise ValueError("%s expects (batch, length), got %s" % (self.NAME, tuple(x.shape)))
+        if not x.is_cuda:
+            raise _hip.AirError("%s HIP path needs a GPU tensor; there is no CPU fallback" % self.NAME)
+
+    def _check_lengths(self, host, Lcap):
+        """Host-side lengths beyond the [1, Lcap] check that ``forward_ragged`` shares with LFCC."""
+
+    @staticmethod
+    def _src(x):
+        if x.dtype == torch.int16:
+            return x.contiguous(), True
+        return (x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()), False
+
+    def _dense(self, x):
+        """(B, L) float32 or int16 on the GPU -> (B, T, out_dim).  Does not mutate ``x``."""
+        self._check(x)
         B, L = x.shape
-        nbytes = lib.air_preemph_ws_bytes(_hip.ci(B), _hip.ci(L))
-        ws = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
-        _hip.check(lib.air_preemph_inplace(_hip.dptr(x), _hip.ci(B), _hip.ci(L), _hip.cf(0.97),
-                                           _hip.dptr(ws), _hip.csz(nbytes), _hip.stream()),
-                   "air_preemph_inplace")
+        self._check_lengths(torch.tensor([L]), L)
+        src, i16 = self._src(x)
+        out = torch.empty((B, 1 + L // self.fs, self.out_dim), device=x.device, dtype=torch.float32)
+        null = _hip.dptr(None, allow_none=True)
+        _hip.check(_hip.lib().air_spec_fwd(_hip.ci(self.KIND), null if i16 else _hip.dptr(src),
+                                           _hip.dptr(src, torch.int16) if i16 else null, _hip.ci(B), _hip.ci(L),
+                                           _hip.dptr(out), _hip.dptr(self.plan(x.device), torch.uint8),
+                                           _hip.ci(self._flags()), _hip.stream()), "air_spec_fwd")
+        return out, src
+
+    def _padded(self, x, lengths, feat_len, start, padding):
+        mode = pad_mode_id(padding)
+        B, Lcap = x.shape
+        if start is not None and not (torch.is_tensor(start) and start.is_cuda):
+            start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
+        src, i16 = self._src(x)
+        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
+        null = _hip.dptr(None, allow_none=True)
+        _hip.check(_hip.lib().air_spec_fwd_ragged(_hip.ci(self.KIND), null if i16 else _hip.dptr(src),
+                                                  _hip.dptr(src, torch.int16) if i16 else null, _hip.ci(B), _hip.ci(Lcap),
+                                                  _hip.dptr(lengths, torch.int32, True), _hip.dptr(out), _hip.ci(feat_len),
+                                                  _hip.dptr(start, torch.int32, True),
+                                                  _hip.dptr(self.plan(x.device), torch.uint8), _hip.ci(self._flags()),
+                                                  _hip.ci(mode), _hip.stream()), "air_spec_fwd_ragged")
+        return out
+
+    def forward_padded(self, x, feat_len=750, start=None, padding="repeat"):
+        """Fused front-end -> pad / chop -> transpose: (B, L) -> (B, out_dim, feat_len), what dataset.py:62-79 +
+        main_train.py:338 build on the host.  Does not mutate ``x``.  ``start`` / ``padding``: as in
+        ``LFCC.forward_padded``, without 'silence' (NotImplementedError)."""
+        self._check(x, padding)
+        self._check_lengths(torch.tensor([x.shape[1]]), x.shape[1])
+        return self._padded(x, None, feat_len, start, padding)
+
+    def forward_ragged(self, x, lengths, feat_len=750, start=None, padding="repeat"):
+        """Utterances of different lengths in one launch: row b of ``x`` (B, Lcap) holds ``lengths[b]`` samples ->
+        (B, out_dim, feat_len), row b being what ``forward_padded`` gives for that utterance alone.  ``lengths``: as in
+        ``LFCC.forward_ragged`` - a GPU tensor is used as is (the kernel clamps it to [1, Lcap]), a host tensor or list
+        is checked (ValueError) and uploaded."""
+        self._check(x, padding)
+        B, Lcap = x.shape
+        if not (torch.is_tensor(lengths) and lengths.is_cuda):
+            host = torch.as_tensor(lengths).reshape(-1)
+            if host.numel() != B or host.is_floating_point():
+                raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
+            if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
+                raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
+                    Lcap, int(host.min()), int(host.max())))
+            self._check_lengths(host, Lcap)
+            lengths = host.to(torch.int32).to(x.device)
+        elif lengths.numel() != B:
+            raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
+        return self._padded(x, lengths.to(torch.int32).contiguous(), feat_len, start, padding)
+
+
+class STFT(_Spectral):
+    """STFT(fl, fs, fn, sr, with_emphasis=True): drop-in for the reference's power spectrogram
+    (feature_extraction.py:141-165).  ``forward(x:(B, L)) -> (B, 1 + L // fs, fn // 2 + 1)``, |X|^2 without a log, with the
+    reference's in-place pre-emphasis of the caller's tensor (:157) unless ``mutate_input`` is False.  One fused HIP
+    kernel (csrc/spectral.hip); only the geometry the reference uses, (320, 160, 512) (preprocess.py:40), is built."""
+    KIND, NAME = 1, "STFT"
+
+    def __init__(self, fl, fs, fn, sr, with_emphasis=True):
+        super().__init__()
+        if (fl, fs, fn) != (320, 160, 512):
+            raise NotImplementedError("STFT is built for (fl, fs, fn) = (320, 160, 512) only (preprocess.py:40), got %s"
+                                      % ((fl, fs, fn),))
+        self.fl, self.fs, self.fn, self.sr = fl, fs, fn, sr
+        self.with_emphasis = with_emphasis
+        self.mutate_input = True  # reference behaviour (feature_extraction.py:157)
+
+    @property
+    def out_dim(self):
+        return self.fn // 2 + 1
+
+    def _flags(self):
+        return 1 if self.with_emphasis else 0
+
+    def forward(self, x):
+        out, src = self._dense(x)
+        if self.with_emphasis and self.mutate_input and x.dtype != torch.int16:  # (integers: nothing to mutate)
+            preemph_inplace_(src)
+            if src is not x:
+                x.copy_(src)
+        return out
+
+
+class Melspec(_Spectral):
+    """Melspec(): the reference's mel spectrogram (feature_extraction.py:168-176), i.e.
+    ``librosa.feature.melspectrogram(y, sr=16000, n_fft=512, hop_length=128)``: 128 Slaney bands of the power
+    spectrogram, no log.  ``forward(x)`` reads ``x[0]`` only and returns (128, T) like the reference (:175-176);
+    ``forward_batch(x)`` returns (B, 128, T).  ``pad_mode``: 'reflect' (librosa's default when the reference was
+    written) or 'constant' (its default since 0.10).  Defined by the formulas in csrc/spectral.hip; parity with librosa
+    itself is not pinned (INTEGRATION.md)."""
+    KIND, NAME = 2, "Melspec"
+    fs = 128       # hop
+    out_dim = 128
+
+    def __init__(self, pad_mode="reflect"):
+        super().__init__()
+        if pad_mode not in ("reflect", "constant"):
+            raise ValueError("pad_mode must be 'reflect' or 'constant', got %r" % (pad_mode,))
+        self.pad_mode = pad_mode
+
+    def _flags(self):
+        return 2 if self.pad_mode == "reflect" else 0
+
+    def _check_lengths(self, host, Lcap):
+        if self.pad_mode == "reflect" and host.numel() and int(host.min()) < 257:
+            raise ValueError("pad_mode='reflect' reflects 256 samples at either end and needs utterances of at least 257 "
+                             "samples (numpy raises too), got %d; use pad_mode='constant'" % int(host.min()))
+
+    def forward_frames(self, x):
+        """(B, L) -> (B, T, 128): the frame-major layout of ``LFCC.forward`` / ``STFT.forward``."""
+        return self._dense(x)[0]
+
+    def forward_batch(self, x):
+        """(B, L) -> (B, 128, T), written in that layout by the kernel (``forward_padded`` at feat_len = T)."""
+        self._check(x)
+        return self.forward_padded(x, 1 + x.shape[1] // self.fs)
+
+    def forward(self, x):
+        return self.forward_batch(x[:1])[0]

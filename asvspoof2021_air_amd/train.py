@@ -70,7 +70,7 @@ class Trainer:
 
     def __init__(self, model, enc_dim=256, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, r_real=0.9,
                  r_fake=0.2, alpha=20.0, weight_loss=1.0, feat_len=750, device="cuda", ecapa=False,
-                 loss_module=None, augment=None, padding="repeat", add_loss="ang_iso"):
+                 loss_module=None, augment=None, padding="repeat", add_loss="ang_iso", frontend=None):
         """add_loss: the training head (module docstring).  An explicit ``loss_module`` of one of the head classes
         selects its head; any other module is driven as the OC-Softmax head."""
         if add_loss not in ADD_LOSSES:
@@ -87,8 +87,13 @@ class Trainer:
         if add_loss is None:
             from .adversarial import CrossEntropyLoss
             self.ce = CrossEntropyLoss()  # main_train.py:251
-        self.lfcc = LFCC(320, 160, 512, 16000, 20, with_energy=False).to(self.device)
-        self.lfcc.mutate_input = False
+        # the front-end of features() / score() / the captured step: None = the reference's LFCC (dataset.py:13); a given
+        # module (feature_extraction.STFT / Melspec) takes its place - (B, out_dim, feat_len) from forward_padded / _ragged
+        # (forward_padded / forward_ragged, the only entry points used here, never mutate the waveforms)
+        if frontend is None:
+            frontend = LFCC(320, 160, 512, 16000, 20, with_energy=False)
+            frontend.mutate_input = False
+        self.lfcc = frontend.to(self.device)
         self.lr0 = lr
         self.feat_optimizer = FusedAdam(self.model, lr=lr, betas=betas, eps=eps, weight_decay=0.0005)
         self.loss_optimizer = FusedSGD(self.loss, lr=lr) if self.loss is not None else None
@@ -243,7 +248,7 @@ class Trainer:
             self._refuse_ragged_augment(lengths)
             feat = self.lfcc.forward_ragged(pcm, lengths, self.feat_len, start, self.padding)
         else:
-            feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, 60, feat_len)
+            feat = self.lfcc.forward_padded(pcm, self.feat_len, start, self.padding)  # (B, out_dim, feat_len)
         return feat if self.ecapa else feat.unsqueeze(1)
 
     def _refuse_ragged_augment(self, lengths):
@@ -484,7 +489,8 @@ class Trainer:
         return (tuple(pcm.shape), pcm.dtype, tuple(labels.shape), getattr(self.model, "compute_dtype", "fp32"),
                 self.feat_len, float(self.weight_loss)) + self._head_scalars() + (
                 self.padding, getattr(self.model, "noise_mode", None), getattr(self.model, "noise_scale", None)) + (
-                ("ragged",) if ragged else ())
+                ("ragged",) if ragged else ()) + (
+                () if type(self.lfcc) is LFCC else (type(self.lfcc).__name__, self.lfcc.out_dim, self.lfcc._flags()))
 
     def _graphed_step(self, pcm, labels, lengths=None, start=None):
         from . import ops

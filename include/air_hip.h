@@ -149,6 +149,43 @@ int air_pad_transpose(const float* feat, int B, int T, int D, float* out, int fe
 int air_pad_transpose_ex(const float* feat, int B, int T, int D, float* out, int feat_len,
                          const int* start_dev, int pad_mode, const float* silence_dev, air_stream_t stream);
 
+/* ---------------------------------------------------- STFT and Melspec --
+ * The reference's two other front-ends, each one launch from PCM (csrc/spectral.hip):
+ *   AIR_SPEC_STFT  replaces STFT.forward (feature_extraction.py:154-165; dumped by preprocess.py:35-47): optional
+ *                  pre-emphasis 0.97 (:157), torch.stft(x, 512, 160, 320, hamming_window(320), pad_mode="constant")
+ *                  (:159-161), norm(., 2, -1).pow(2) (:163).  T = 1 + L / 160, D = 257, no log.
+ *   AIR_SPEC_MEL   replaces Melspec.forward (feature_extraction.py:174-176; preprocess.py:176-215, :247-258):
+ *                  librosa.feature.melspectrogram(sr=16000, n_fft=512, hop_length=128) - periodic Hann window of 512,
+ *                  centred frames with 256 reflected (AIR_SPEC_REFLECT) or zero samples each side, power 2.0, the
+ *                  128-band Slaney mel filterbank with Slaney normalisation.  T = 1 + L / 128, D = 128, no log.
+ * These are the only geometries.  The plan blob (built on the host, uploaded by the caller) is
+ *   int32[8]  kind, D, hop, window length, 257, widest mel filter, 0, 0
+ *   float[512] window (STFT: 320 taps, then zeros)   float[512] + float[32] FFT twiddles
+ *   int32[128] first bin of mel filter j             int32[128] bins it spans
+ *   float[12][128] weight of bin first[j] + i in filter j, fp64 formulas rounded once (zero for STFT). */
+#define AIR_SPEC_STFT 1
+#define AIR_SPEC_MEL 2
+#define AIR_SPEC_EMPHASIS 1 /* STFT: pre-emphasis 0.97 on the original samples (feature_extraction.py:157) */
+#define AIR_SPEC_REFLECT 2  /* MEL: pad_mode "reflect" (librosa's default before 0.10); unset: "constant" */
+size_t air_spec_plan_bytes(void);
+int air_spec_plan_build(int kind, void* plan_host_out);
+/* D of a kind: 257 / 128 (AIR_EINVAL for anything else). */
+int air_spec_out_dim(int kind);
+/* Exactly one of pcm (B, L) fp32 / pcm16 (16-bit PCM, x = s / 32768) is non-NULL; neither is modified.
+ * out: (B, 1 + L / hop, D).  A plan of the other kind: nothing is written. */
+int air_spec_fwd(int kind, const float* pcm, const int16_t* pcm16, int B, int L, float* out, const void* plan_dev,
+                 int flags, air_stream_t stream);
+/* The model-input layout (dataset.py:62-79 pad / chop + main_train.py:338 transpose): out is (B, D, feat_len).  Row b
+ * holds L_b = clamp(lengths_dev[b], 1, Lcap) samples (lengths_dev NULL: every row holds Lcap); no sample at index
+ * >= L_b is read.  T_b > feat_len: chopped at start_dev[b], clamped to [0, T_b - feat_len] (NULL = 0); T_b < feat_len:
+ * AIR_PAD_REPEAT tiles the frames (dataset.py:519-522), AIR_PAD_ZERO appends zero frames (:513-517).
+ * AIR_PAD_SILENCE: AIR_EUNSUPPORTED - the reference's silence frame is an LFCC frame (dataset.py:13-16).  Under
+ * AIR_SPEC_REFLECT a row shorter than 257 samples has no reflection to read (numpy raises); its indices are clamped
+ * into the row.  One launch of B x ceil((1 + Lcap / hop) / 32) workgroups; those a row does not need return at once. */
+int air_spec_fwd_ragged(int kind, const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev,
+                        float* out, int feat_len, const int* start_dev, const void* plan_dev, int flags, int pad_mode,
+                        air_stream_t stream);
+
 /* --------------------------------------------------------------- conv2d --
  * Replaces nn.Conv2d forward/backward as used by resnet.py:131,56-61,140
  * (bias=False everywhere).  NCHW fp32.  Implicit GEMM on f32 MFMA.

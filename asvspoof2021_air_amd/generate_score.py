@@ -16,6 +16,10 @@ the true key instead.
 
 ``score_pcm`` is the on-the-fly variant: raw PCM -> fused HIP LFCC (+pad/chop, transposed) ->
 model -> score, for corpora that were not pre-extracted by preprocess.py.
+
+``test_on_dataset_ensemble`` / ``score_pcm_ensemble`` score K models in one pass - the batch is copied and transposed
+(or its features computed) once for all of them - and fuse the K score vectors on the device as the reference's
+score_fusion.py does on files (score_fusion.py here; ops.score_fuse).
 """
 import os
 
@@ -160,3 +164,133 @@ def score_pcm(model, loss_model, pcm, feat_len=750, ecapa=False, add_loss="ocsof
         feat = lfcc.forward_padded(pcm, feat_len, start)
     model.eval()
     return -batch_scores(model, feat if ecapa else feat.unsqueeze(1), loss_model, add_loss)
+
+
+# ------------------------------------------------------------------ K systems in one pass (score_fusion.py)
+def _per_model(value, K, what):
+    """One entry per model from a single value or a list of K."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != K:
+            raise ValueError("%s: %d entries for %d models" % (what, len(value), K))
+        return list(value)
+    return [value] * K
+
+
+@torch.no_grad()
+def score_pcm_ensemble(models, loss_models, pcm, feat_len=750, ecapa=False, add_loss="ocsoftmax", lfcc=None, lengths=None,
+                       start=None):
+    """score_pcm for K models on ONE front-end launch: (B, L) raw PCM -> (K, B) scores as written to the files, row k
+    bit-equal to ``score_pcm(models[k], loss_models[k], pcm, ...)``.  ``loss_models`` / ``ecapa`` / ``add_loss``: one
+    value for all models or a list of K; the feature tensor is computed once, a 2-d model gets ``unsqueeze(1)`` of it
+    (a view)."""
+    K = len(models)
+    if K < 1:
+        raise ValueError("score_pcm_ensemble needs at least one model")
+    loss_models, ecapa, add_loss = (_per_model(v, K, n) for v, n in ((loss_models, "loss_models"), (ecapa, "ecapa"),
+                                                                     (add_loss, "add_loss")))
+    if lfcc is None:
+        lfcc = LFCC(320, 160, 512, 16000, 20, with_energy=False).to(pcm.device)
+        lfcc.mutate_input = False
+    if lengths is not None:
+        feat = lfcc.forward_ragged(pcm, lengths, feat_len, start)
+    else:
+        feat = lfcc.forward_padded(pcm, feat_len, start)
+    feat4 = feat.unsqueeze(1)
+    out = torch.empty((K, feat.shape[0]), dtype=torch.float32, device=feat.device)
+    for k, model in enumerate(models):
+        model.eval()
+        out[k].copy_(-batch_scores(model, feat if ecapa[k] else feat4, loss_models[k], add_loss[k]))
+    return out
+
+
+@torch.no_grad()
+def test_on_dataset_ensemble(models, loader, score_files, fused_file=None, method="avg", eers=None, loss_models=None,
+                             add_loss=None, task="19eval", ecapa=False, device="cuda", keep_dataset_labels=False):
+    """``test_on_dataset(..., sync="end")`` for K models in ONE pass over ``loader``, and their fusion.
+
+    Per batch: one host-to-device copy and one transpose of the features, shared by the K models (an ECAPA model takes
+    the ``squeeze(1)`` view of the same tensor), then K ``batch_scores`` calls whose results are copied device-side into
+    a (K, capacity) buffer (capacity from ``len(loader)``, doubled by a device-side copy when outgrown).  Nothing inside
+    the loop waits for the device.  Behind the loop ops.score_fuse fuses the K rows where they lie (aligned path:
+    ``method`` "avg" = the sum, "wght" = the weighted mean with ``score_fusion.cal_weight(eers)``), and ONE
+    device-to-host copy brings back the K vectors and the fused one.
+
+    Written: ``score_files[k]`` with exactly the text ``test_on_dataset(models[k], ..., sync="end")`` writes;
+    ``fused_file`` (optional, '19' tasks: the 2021 files carry no key to join on) with the text
+    ``score_fusion.write_fused`` produces from ``avg_fuse`` / ``weighted_fuse`` over those K files - rows
+    ``fname - key score`` sorted by name.  A name that the loader yields twice with one key is refused (ValueError): the
+    file-based fusion would add the two.  ``loss_models`` / ``add_loss`` / ``ecapa``: one value for all models or a
+    list of K.  Every model is put in eval mode.
+
+    Returns (lines per file, FusionResult or None).  The FusionResult (score_fusion.fuse_device: the systems' EERs, the
+    fused EER) is computed for '19' tasks with ``keep_dataset_labels``, where the keys are the true ones; it costs
+    fuse_device's own copy of the records (two for "wght" without ``eers``, whose weights then come from the systems'
+    own EERs).  Without it "wght" needs ``eers``.
+
+    ``use_graph`` (GraphedScorer) is out of scope here: K captured graphs per batch shape would share one static input
+    but not one replay."""
+    from . import score_fusion as sf
+    K = len(models)
+    if K < 1 or len(score_files) != K:
+        raise ValueError("%d score files for %d models" % (len(score_files), K))
+    if method not in ("avg", "wght"):
+        raise ValueError("method must be 'avg' or 'wght', got %r" % (method,))
+    loss_models, ecapa, add_loss = (_per_model(v, K, n) for v, n in ((loss_models, "loss_models"), (ecapa, "ecapa"),
+                                                                     (add_loss, "add_loss")))
+    is19 = "19" in task
+    evaluate = is19 and keep_dataset_labels
+    if fused_file is not None and not is19:
+        raise ValueError("a fused file needs the keys of a '19' task")
+    if method == "wght" and eers is None and not evaluate:
+        raise ValueError("method 'wght' needs eers (or a '19' task with keep_dataset_labels, whose EERs it then takes)")
+    if eers is not None and (method != "wght" or len(eers) != K):
+        raise ValueError("eers: %d EERs for method 'wght', one per model" % K)
+    for m in models:
+        m.eval()
+    held, n, rows = None, 0, []
+    for data in loader:
+        lfcc4 = data[0].to(device).transpose(2, 3).contiguous()
+        lfcc3 = lfcc4.squeeze(1)
+        B = lfcc4.shape[0]
+        if held is None:
+            held = torch.empty((K, max(1, (len(loader) if hasattr(loader, "__len__") else 64) * B)), dtype=torch.float32,
+                               device=lfcc4.device)
+        if n + B > held.shape[1]:
+            grown = torch.empty((K, max(n + B, 2 * held.shape[1])), dtype=torch.float32, device=held.device)
+            grown[:, :n].copy_(held[:, :n])
+            held = grown
+        for k, model in enumerate(models):
+            score = batch_scores(model, lfcc3 if ecapa[k] else lfcc4, loss_models[k], add_loss[k])
+            held[k, n:n + B].copy_((-score).float())
+        labels = data[3] if is19 else None
+        rows.extend((data[1][j], (int(labels[j]) if keep_dataset_labels else 0) if is19 else None) for j in range(B))
+        n += B
+    if held is None:
+        raise ValueError("test_on_dataset_ensemble needs at least one batch")
+    per_system = held[:, :n]
+    result = None
+    if evaluate:
+        labs = torch.tensor([lab for _, lab in rows], dtype=torch.int64).to(held.device)
+        result = sf.fuse_device(per_system, labs, method, eers)
+        fused = result.scores
+    else:
+        weights = None
+        if method == "wght":
+            weights = torch.tensor(sf.cal_weight(eers), dtype=torch.float64).to(torch.float32).to(held.device)
+        fused = ops.score_fuse(per_system, None, weights, "mean" if method == "wght" else "sum")
+    host = torch.cat((per_system.reshape(-1), fused)).cpu()  # [K vectors | fused]: the one copy
+    keys = [None if lab is None else ("spoof" if lab else "bonafide") for _, lab in rows]
+    for k, path in enumerate(score_files):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fh:
+            for (name, _), key, v in zip(rows, keys, host[k * n:(k + 1) * n].tolist()):
+                fh.write(format_score_line(name, v, key))
+    if fused_file is not None:
+        joined = [(name, "-", key) for (name, _), key in zip(rows, keys)]
+        order = sorted(range(n), key=joined.__getitem__)
+        for a, b in zip(order, order[1:]):
+            if joined[a] == joined[b]:
+                raise ValueError("the loader yields %r twice: score_fusion would add the two scores" % (joined[a],))
+        os.makedirs(os.path.dirname(os.path.abspath(fused_file)), exist_ok=True)
+        sf.write_fused(fused_file, [joined[i] for i in order], host[K * n:].numpy()[order])
+    return n, result

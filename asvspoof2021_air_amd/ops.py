@@ -1297,6 +1297,58 @@ def eval_sorted_keys(scores, labels, negate=False):
     return ws[:n * 8].view(torch.int64).clone()
 
 
+# ---------------------------------------------------------------- score fusion (csrc/score_fusion.hip)
+SCORE_FUSE_MODES = {"sum": 0, "mean": 1}
+
+
+def score_fuse_max_systems():
+    return int(_hip.lib().air_score_fuse_max_systems())
+
+
+def score_fuse(scores, index=None, weights=None, mode="sum", out=None, n_present=None):
+    """The fusion of K systems' scores (air_score_fuse): ``scores`` fp32 (K, L) on the GPU, rows of unit stride (the
+    row stride may exceed L: rows of a wider buffer); ``index`` None - trial n is column n, N = L - or int32 (K, N), the
+    position of trial n in row k, negative = absent (positions >= L are made absent by one elementwise launch before the
+    kernel: nothing outside a row is read); ``weights`` None or fp32 (K,) on the GPU; ``mode`` "sum" (avg_fuse) or
+    "mean" over the systems that have the trial (weighted_fuse).  Returns the fused fp32 (N,) tensor (``out``);
+    ``n_present``: optional int32 (N,) that gets the number of terms per trial (0: the trial's score is NaN).
+    Enqueues only: nothing is synchronised."""
+    if not torch.is_tensor(scores) or not scores.is_cuda:
+        raise _hip.AirError("scores must be a GPU tensor (the HIP path has no CPU fallback)")
+    if mode not in SCORE_FUSE_MODES:
+        raise ValueError("mode must be 'sum' or 'mean', got %r" % (mode,))
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError("scores must be fp32 of shape (K, L), got %s %s" % (scores.dtype, tuple(scores.shape)))
+    K, L = scores.shape
+    if K < 1 or K > score_fuse_max_systems():
+        raise ValueError("score fusion takes 1 .. %d systems, got %d" % (score_fuse_max_systems(), K))
+    if L > 0 and (scores.stride(1) != 1 or (K > 1 and scores.stride(0) < L)):
+        scores = scores.contiguous()
+    N = L
+    if index is not None:
+        if not torch.is_tensor(index) or not index.is_cuda or index.dtype != torch.int32 or index.dim() != 2 or index.shape[0] != K:
+            raise ValueError("index must be an int32 GPU tensor of shape (%d, N)" % K)
+        N = index.shape[1]
+        index = torch.where(index < L, index, -1).contiguous()
+    if weights is not None and (not torch.is_tensor(weights) or weights.numel() != K):
+        raise ValueError("weights must be %d fp32 values on the GPU" % K)
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=scores.device)
+    elif out.dim() != 1 or out.numel() != N:
+        raise ValueError("out must be fp32 of shape (%d,)" % N)
+    if n_present is not None and (n_present.dim() != 1 or n_present.numel() != N):
+        raise ValueError("n_present must be int32 of shape (%d,)" % N)
+    if N == 0:
+        return out
+    if L == 0:
+        raise ValueError("the rows of scores are empty")
+    _hip.check(_hip.lib().air_score_fuse(
+        ctypes.c_void_p(scores.data_ptr()), ctypes.c_int64(scores.stride(0) if K > 1 else L),
+        dptr(index, torch.int32, allow_none=True), dptr(weights, torch.float32, allow_none=True), ci(K), ctypes.c_int64(N),
+        ci(SCORE_FUSE_MODES[mode]), dptr(out), dptr(n_present, torch.int32, allow_none=True), stream()), "air_score_fuse")
+    return out
+
+
 # BatchNorm's num_batches_tracked counters: one multi-tensor add per forward instead of one 4 us ATen launch per
 # layer (34 per ECAPA step).  bn_tick() queues a counter, bn_flush() adds 1 to everything queued since the last flush.
 _TICKS = []

@@ -1107,6 +1107,27 @@ int air_eval_sort_keys(int n, void* ws, size_t ws_bytes, air_stream_t stream);
 int air_eval_curve_min(int n, int want_dcf, double c1, double c2, air_eval_record* rec, void* ws, size_t ws_bytes,
                        air_stream_t stream);
 
+/* -------------------------------------------------------- score fusion ---
+ * The fusion of the scores of K systems as the reference's score_fusion.py computes it with pandas: out[n] = the sum
+ * (mode 0: avg_fuse, score_fusion.py:21-28) or the mean over the systems that have the trial (mode 1: weighted_fuse,
+ * :31-43) of weights[k] * score of trial n in system k, k = 0 .. K-1 in that order, as a compensated (Kahan) fp32
+ * accumulation: v = score * weight rounded to fp32 on its own (no product without weights); y = v - c; t = s + y;
+ * c = (t - s) - y, reset to 0 where it is NaN (an infinite term); s = t - every step one correctly rounded fp32
+ * operation, never contracted.  A NaN v is skipped and not counted.  The mean is s / (float)count, one fp32 division.
+ *
+ * scores: K rows, system-major, row k at scores + k * row_stride.  index NULL (aligned): trial n is element n of every
+ * row (coalesced reads; row_stride >= N for K > 1).  index (K x N int32, device): index[k * N + n] is the position of
+ * trial n in row k, negative = system k does not have it (a gather); positions must lie in [0, row_stride), anything
+ * else counts as absent and is never dereferenced.  weights: K fp32 in DEVICE memory (a captured graph replays with new
+ * weights) or NULL.  n_present (N uint32 or NULL) gets the number of terms counted; a trial without any gets NaN and 0
+ * (pandas has no such row; its sum over a group whose every score is NaN is 0.0 - here NaN as well).
+ * N = 0: nothing is launched.  AIR_EINVAL: K < 1, N < 0, a mode other than 0 | 1, scores or out NULL, a row_stride
+ * below the row, out overlapping the K rows; AIR_EUNSUPPORTED: K > air_score_fuse_max_systems(), N or row_stride above
+ * 2^38 - all ahead of any HIP call, out untouched. */
+int air_score_fuse_max_systems(void); /* 64 */
+int air_score_fuse(const float* scores, int64_t row_stride, const int32_t* index, const float* weights, int K, int64_t N,
+                   int mode, float* out, uint32_t* n_present, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

@@ -56,6 +56,11 @@ class AirAdvHeads(ctypes.Structure):
                 ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t), ("head", AirAdvHead * ADV_MAX_HEADS)]
 
 
+class AirTsneSchedule(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("max_iter", "exploration_iter", "n_iter_check", "n_iter_without_progress")] + [
+        ("learning_rate", ctypes.c_float), ("early_exaggeration", ctypes.c_float), ("min_grad_norm", ctypes.c_double)]
+
+
 def lib_path():
     return _LIB_PATH
 
@@ -94,7 +99,7 @@ def lib():
                      "air_channel_sum_ws_bytes", "air_ir_convolve_ws_bytes", "air_ir_convolve_ws_bytes_ex", "air_ir_bank_ws_bytes", "air_g711_ws_bytes", "air_conv2d_prepack_bytes",
                      "air_conv1d_tap_pack_elems", "air_h_bn_ws_bytes", "air_h_conv1d_ws_bytes", "air_conv2d_fwd_stats_bytes", "air_conv2d_dgrad_bn_sums_bytes", "air_conv2d_dgrad_s2_pair_prepack_bytes", "air_h_conv1d_tap_stats_bytes", "air_h_conv1d_tap_bwd_sums_bytes", "air_h_conv1d_pointwise_stats_bytes",
                      "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes", "air_adv_heads_ws_bytes",
-                     "air_eval_workspace_bytes", "air_eval_workspace_bytes_grouped"):
+                     "air_eval_workspace_bytes", "air_eval_workspace_bytes_grouped", "air_pca_ws_bytes", "air_tsne_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_size_t
     return _lib

@@ -1349,6 +1349,180 @@ def score_fuse(scores, index=None, weights=None, mode="sum", out=None, n_present
     return out
 
 
+# ---------------------------------------------------------------- embedding projections (csrc/embed_vis.hip)
+TSNE_STATUS_BYTES = 64  # air_tsne_status
+TSNE_STATUS_DTYPE = [("stopped", "<i4"), ("reason", "<i4"), ("n_iter", "<i4"), ("best_iter", "<i4"),
+                     ("best_error", "<f8"), ("kl", "<f8"), ("grad_norm", "<f8"), ("pad", "<f8", (3,))]
+
+
+def vis_limits():
+    """(largest N, largest D, most principal components) the projection kernels take."""
+    L = _hip.lib()
+    return int(L.air_vis_max_n()), int(L.air_vis_max_d()), int(L.air_pca_max_components())
+
+
+def _vis_matrix(x, what, cols=None):
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise _hip.AirError("%s must be a GPU tensor (the HIP path has no CPU fallback)" % what)
+    if x.dim() != 2 or x.dtype != torch.float32 or (cols is not None and x.shape[1] != cols):
+        raise ValueError("%s must be fp32 of shape (N, %s), got %s %s" % (what, cols or "D", x.dtype, tuple(x.shape)))
+    return x.contiguous()
+
+
+def _vis_ws(nbytes, device, what):
+    if nbytes == 0:
+        raise _hip.AirError("%s: AIR_EUNSUPPORTED (2 <= N <= %d, D <= %d)" % ((what,) + vis_limits()[:2]))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def pca_ws_bytes(n, d):
+    return int(_hip.lib().air_pca_ws_bytes(ci(int(n)), ci(int(d))))
+
+
+def tsne_ws_bytes(n):
+    return int(_hip.lib().air_tsne_ws_bytes(ci(int(n))))
+
+
+def pca_gram(x, ws=None):
+    """(mean fp32 (D,), centred Gram matrix fp64 (D, D)) of ``x`` fp32 (N, D) on the GPU (air_pca_gram)."""
+    x = _vis_matrix(x, "x")
+    N, D = x.shape
+    if ws is None:
+        ws = _vis_ws(pca_ws_bytes(N, D), x.device, "air_pca_gram")
+    mean = torch.empty(D, dtype=torch.float32, device=x.device)
+    gram = torch.empty(D, D, dtype=torch.float64, device=x.device)
+    _hip.check(_hip.lib().air_pca_gram(dptr(x), ci(N), ci(D), dptr(mean), dptr(gram, torch.float64), dptr(ws, torch.uint8),
+                                       csz(ws.numel()), stream()), "air_pca_gram")
+    return mean, gram
+
+
+def pca_project(x, mean, comps):
+    """(x - mean) comps^T as fp32 (N, K): ``comps`` fp32 (K, D) on the GPU (air_pca_project)."""
+    x = _vis_matrix(x, "x")
+    N, D = x.shape
+    comps = _vis_matrix(comps, "comps", D)
+    K = comps.shape[0]
+    if mean.numel() != D:
+        raise ValueError("mean must hold %d values" % D)
+    out = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    _hip.check(_hip.lib().air_pca_project(dptr(x), ci(N), ci(D), dptr(mean), dptr(comps), ci(K), dptr(out), stream()),
+               "air_pca_project")
+    return out
+
+
+def pairwise_sqdist(x, out=None):
+    """Dense (N, N) fp32 squared Euclidean distances of the rows of ``x`` fp32 (N, D), summed as (x_i - x_j)^2."""
+    x = _vis_matrix(x, "x")
+    N, D = x.shape
+    if out is None:
+        out = torch.empty(N, N, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, N):
+        raise ValueError("out must be fp32 of shape (%d, %d)" % (N, N))
+    _hip.check(_hip.lib().air_pairwise_sqdist(dptr(x), ci(N), ci(D), dptr(out), stream()), "air_pairwise_sqdist")
+    return out
+
+
+def tsne_affinities(dist, perplexity, out=None):
+    """scikit-learn's _binary_search_perplexity over ``dist`` fp32 (N, N): (conditional P fp32 (N, N), beta fp32 (N,))."""
+    dist = _vis_matrix(dist, "dist")
+    N = dist.shape[0]
+    if dist.shape[1] != N:
+        raise ValueError("dist must be square, got %s" % (tuple(dist.shape),))
+    if out is None:
+        out = torch.empty(N, N, dtype=torch.float32, device=dist.device)
+    elif tuple(out.shape) != (N, N) or out.data_ptr() == dist.data_ptr():
+        raise ValueError("out must be another fp32 tensor of shape (%d, %d)" % (N, N))
+    beta = torch.empty(N, dtype=torch.float32, device=dist.device)
+    _hip.check(_hip.lib().air_tsne_affinities(dptr(dist), ci(N), cf(float(perplexity)), dptr(out), dptr(beta), stream()),
+               "air_tsne_affinities")
+    return out, beta
+
+
+def _tsne_ws(N, device, ws, what):
+    if ws is None:
+        return _vis_ws(tsne_ws_bytes(N), device, what)
+    return ws
+
+
+def tsne_joint(cond, ws=None):
+    """The joint distribution of the conditional ``cond`` fp32 (N, N), IN PLACE (air_tsne_joint); returns ``cond``."""
+    if not torch.is_tensor(cond) or not cond.is_cuda:
+        raise _hip.AirError("cond must be a GPU tensor (the HIP path has no CPU fallback)")
+    N = cond.shape[0]
+    if cond.dim() != 2 or cond.shape[1] != N or cond.dtype != torch.float32 or not cond.is_contiguous():
+        raise ValueError("cond must be a contiguous fp32 (N, N) tensor")
+    ws = _tsne_ws(N, cond.device, ws, "air_tsne_joint")
+    _hip.check(_hip.lib().air_tsne_joint(dptr(cond), ci(N), dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_tsne_joint")
+    return cond
+
+
+def tsne_new_status(device):
+    """A device status record (air_tsne_status) that says "running" with no best error yet."""
+    import numpy as np
+    rec = np.zeros(1, dtype=TSNE_STATUS_DTYPE)
+    rec["best_error"] = np.finfo(np.float64).max
+    rec["kl"] = rec["grad_norm"] = np.nan
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+
+
+def tsne_read_status(status):
+    """The status record on the host, as a dict (one device-to-host copy)."""
+    rec = status.cpu().numpy().view(TSNE_STATUS_DTYPE)[0]
+    return {k: rec[k].item() for k in ("stopped", "reason", "n_iter", "best_iter", "best_error", "kl", "grad_norm")}
+
+
+def tsne_gradient_kl(P, y, exaggeration=1.0, ws=None):
+    """(grad fp32 (N, 2), KL as a device fp64 scalar inside the returned status record) of _kl_divergence at the
+    embedding ``y`` for the joint ``P``: air_tsne_pairs with the KL pass, air_tsne_gradient, air_tsne_check without rules.
+    Returns (grad, status): ``tsne_read_status(status)["kl"]``."""
+    P = _vis_matrix(P, "P")
+    N = P.shape[0]
+    y = _vis_matrix(y, "y", 2)
+    if P.shape[1] != N or y.shape[0] != N:
+        raise ValueError("P must be (N, N) and y (N, 2)")
+    ws = _tsne_ws(N, P.device, ws, "air_tsne_pairs")
+    status = tsne_new_status(P.device)
+    grad = torch.empty(N, 2, dtype=torch.float32, device=P.device)
+    L = _hip.lib()
+    wsp, wsn = dptr(ws, torch.uint8), csz(ws.numel())
+    _hip.check(L.air_tsne_pairs(dptr(P), dptr(y), ci(N), cf(float(exaggeration)), ci(1), dptr(status, torch.uint8), wsp, wsn,
+                                stream()), "air_tsne_pairs")
+    _hip.check(L.air_tsne_gradient(ci(N), dptr(grad), wsp, wsn, stream()), "air_tsne_gradient")
+    # (the check kernel sums the norm partials an update leaves: a step of zero length on a scratch embedding writes them)
+    scratch = y.clone()
+    upd, gains = torch.zeros_like(y), torch.ones_like(y)
+    _hip.check(L.air_tsne_update(dptr(scratch), dptr(upd), dptr(gains), ci(N), cf(0.0), cf(0.0), dptr(status, torch.uint8),
+                                 wsp, wsn, stream()), "air_tsne_update")
+    _hip.check(L.air_tsne_check(ci(N), ci(0), ci(1), ci(0), ci(0), ctypes.c_double(0.0), dptr(status, torch.uint8), wsp, wsn,
+                                stream()), "air_tsne_check")
+    return grad, status
+
+
+def tsne_run(P, y, update, gains, status, max_iter=1000, exploration_iter=250, n_iter_check=50,
+             n_iter_without_progress=300, min_grad_norm=1e-7, learning_rate=200.0, early_exaggeration=12.0, ws=None):
+    """Enqueue the whole descent (air_tsne_run) on the joint ``P`` fp32 (N, N): ``y``, ``update``, ``gains`` fp32 (N, 2)
+    are advanced in place (update and gains are initialised by the call), ``status`` (TSNE_STATUS_BYTES uint8 on the
+    GPU) gets the record.  Nothing is synchronised."""
+    P = _vis_matrix(P, "P")
+    N = P.shape[0]
+    for t, name in ((y, "y"), (update, "update"), (gains, "gains")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _hip.AirError("%s must be a GPU tensor (the HIP path has no CPU fallback)" % name)
+        if tuple(t.shape) != (N, 2) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous fp32 (%d, 2) tensor" % (name, N))
+    if P.shape[1] != N:
+        raise ValueError("P must be square")
+    if status.dtype != torch.uint8 or status.numel() != TSNE_STATUS_BYTES:
+        raise ValueError("status must be %d uint8" % TSNE_STATUS_BYTES)
+    ws = _tsne_ws(N, P.device, ws, "air_tsne_run")
+    sched = _hip.AirTsneSchedule(int(max_iter), int(exploration_iter), int(n_iter_check), int(n_iter_without_progress),
+                                 float(learning_rate), float(early_exaggeration), float(min_grad_norm))
+    _hip.check(_hip.lib().air_tsne_run(dptr(P), dptr(y), dptr(update), dptr(gains), ci(N), ctypes.byref(sched),
+                                       dptr(status, torch.uint8), dptr(ws, torch.uint8), csz(ws.numel()), stream()),
+               "air_tsne_run")
+    return status
+
+
 # BatchNorm's num_batches_tracked counters: one multi-tensor add per forward instead of one 4 us ATen launch per
 # layer (34 per ECAPA step).  bn_tick() queues a counter, bn_flush() adds 1 to everything queued since the last flush.
 _TICKS = []

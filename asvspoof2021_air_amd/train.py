@@ -38,8 +38,11 @@ def adjust_learning_rate(lr0, optimizer, epoch_num, lr_decay=0.5, interval=30):
 # ``tdcf``) and the pass's scores and labels, still on the device
 class EvalResult(collections.namedtuple("EvalResult", ("loss", "eer", "min_tdcf", "scores", "labels"))):
     """Five fields, as callers unpack it; ``by_group`` hangs off it as an attribute: None, or with
-    ``evaluate(n_groups=...)`` one GroupResult per group (None for a group without bona fide or without spoof trials)."""
+    ``evaluate(n_groups=...)`` one GroupResult per group (None for a group without bona fide or without spoof trials);
+    ``feats`` likewise: None, or with ``evaluate(keep_feats=True)`` the pass's embeddings, fp32 (trials, enc_dim), on
+    the device."""
     by_group = None
+    feats = None
 
 
 # one row of the breakdown: the group's name (its index without ``group_names``), the EER of (scores, -scores), and the
@@ -309,20 +312,26 @@ class Trainer:
         """The dev pass of main_train.py:526-575 for one batch: (loss, score) with the reference's score of each head -
         softmax(logits)[:, 0] (None), |feats - center| (isolate / iso_sq), the head's second output (ang_iso, p2sgrad).
         Eval-mode model; feeds ``save_checkpoint(val_loss=...)`` for any head."""
+        return self._eval_batch(pcm, labels, start, lengths)[:2]
+
+    def _eval_batch(self, pcm, labels, start=None, lengths=None):
+        """eval_batch plus the embeddings the model returned: (loss, score, feats)."""
         from . import ops
         self.model.eval()
         feats, logits = self.model(self.features(pcm, start, lengths))
         labels = labels.to(device=feats.device, dtype=torch.int64).contiguous()
         if self.add_loss is None:
-            return self.ce(logits, labels), ops.softmax_rows(logits)[:, 0]
+            return self.ce(logits, labels), ops.softmax_rows(logits)[:, 0], feats
         if self.add_loss in ("isolate", "iso_sq"):
             lm = self.loss
             return ops.isolate_fwd(feats.float().contiguous(), lm.center.detach().contiguous(), labels, float(lm.r_real),
-                                   float(lm.r_fake), self.add_loss == "iso_sq", want_dist=True)
-        return self.loss(feats, labels)
+                                   float(lm.r_fake), self.add_loss == "iso_sq", want_dist=True) + (feats,)
+        loss, score = self.loss(feats, labels)
+        return loss, score, feats
 
     @torch.no_grad()
-    def evaluate(self, batches, epoch_num=None, log=None, capacity=None, tdcf=None, n_groups=None, group_names=None):
+    def evaluate(self, batches, epoch_num=None, log=None, capacity=None, tdcf=None, n_groups=None, group_names=None,
+                 keep_feats=False):
         """The dev / eval half of the reference's epoch (main_train.py:484-668) over ``batches``, an iterable of
         ``(pcm, labels[, start[, lengths]])`` as eval_batch takes them, without a host synchronisation inside the
         loop: per batch eval_batch, the loss into a device vector, scores and labels into device buffers
@@ -345,7 +354,13 @@ class Trainer:
         result's ``by_group`` is a list of GroupResult (``group_names``: G names for them), None where a group lacks a
         class.  ``tdcf`` may carry a fifth element, one (Pfa_asv, Pmiss_asv, Pmiss_spoof_asv) per group; without it
         every group takes the pooled rates.  Without ``n_groups`` the same kernel chain runs on the pooled record alone
-        (as many launches as the pass had before the breakdown, and nothing uploaded); ``by_group`` is None."""
+        (as many launches as the pass had before the breakdown, and nothing uploaded); ``by_group`` is None.
+
+        ``keep_feats=True``: each batch's embeddings - the fp32 (B, enc_dim) tensor the model hands the head - go into
+        a fourth device buffer, preallocated and grown like the others, and come back as the result's ``feats``
+        (trials, enc_dim): what visualize.get_features projects, without a second pass or a ``.cpu()`` per batch.  No
+        synchronisation is added and every other field is bit-equal to the pass without the keyword, which allocates
+        no such buffer and launches what it launched before."""
         from .devbuf import DeviceVector
         from .eval_metrics import DeviceGroupedMinima, _rates_of_group, tdcf_weights
         from .ops import EVAL_MAX_GROUPS, EVAL_RECORD_WORDS
@@ -365,23 +380,29 @@ class Trainer:
                 rates = _rates_of_group(tdcf[4] if len(tdcf) > 4 else tdcf[:3], n_groups)
                 weights = [weights] + [tdcf_weights(*r, tdcf[3]) for r in rates]
         n_batches = len(batches) if hasattr(batches, "__len__") else None
-        losses = scores = labs = grps = None
+        losses = scores = labs = grps = embs = None
+        enc_dim = 0
         for batch in batches:
             if grouped and len(batch) != 5:
                 raise ValueError("with n_groups a batch is (pcm, labels, start, lengths, groups), got %d items" % len(batch))
             pcm = batch[0]
             labels = batch[1].to(device=self.device, dtype=torch.int64, non_blocking=True).contiguous()
-            loss, score = self.eval_batch(pcm, labels, batch[2] if len(batch) > 2 else None,
-                                          batch[3] if len(batch) > 3 else None)
+            loss, score, feats = self._eval_batch(pcm, labels, batch[2] if len(batch) > 2 else None,
+                                                  batch[3] if len(batch) > 3 else None)
             if losses is None:
                 trials = capacity if capacity is not None else (n_batches or 0) * pcm.shape[0]
                 losses = DeviceVector(torch.float32, self.device, n_batches or 64)
                 scores = DeviceVector(torch.float32, self.device, trials)
                 labs = DeviceVector(torch.int64, self.device, trials)
                 grps = DeviceVector(torch.int64, self.device, trials) if grouped else None
+                if keep_feats:
+                    enc_dim = feats.shape[1]
+                    embs = DeviceVector(torch.float32, self.device, trials * enc_dim)
             losses.append(loss)
             scores.append(score)
             labs.append(labels)
+            if keep_feats:
+                embs.append(feats)
             if grouped:
                 grps.append(batch[4].to(device=self.device, dtype=torch.int64, non_blocking=True))
         if losses is None:
@@ -403,6 +424,8 @@ class Trainer:
         if log is not None:
             self.log_eval(epoch_num, batch_losses, eer, name=log)
         out = EvalResult(float(np.nanmean(batch_losses)), eer, min_tdcf, scores.view(), labs.view())
+        if keep_feats:
+            out.feats = embs.view().view(-1, enc_dim)
         if grouped:
             out.by_group = []
             for g in range(n_groups):

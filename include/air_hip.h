@@ -1128,6 +1128,82 @@ int air_score_fuse_max_systems(void); /* 64 */
 int air_score_fuse(const float* scores, int64_t row_stride, const int32_t* index, const float* weights, int K, int64_t N,
                    int mode, float* out, uint32_t* n_present, air_stream_t stream);
 
+/* ------------------------------------------------ embedding projections ---
+ * What the reference's visualize.py asks of scikit-learn, on the device (csrc/embed_vis.hip): PCA without its
+ * eigensolver, and exact t-SNE - TSNE(method="exact") - in two output dimensions with the Euclidean metric.
+ * LIMITS: 2 <= N <= 16384 rows (air_vis_max_n), 1 <= D <= 1024 features (air_vis_max_d), at most 16 principal components
+ * (air_pca_max_components).  Outside them (N < 2 included) the size queries return 0 and the calls AIR_EUNSUPPORTED
+ * (AIR_EINVAL for D < 1 or a NULL pointer).  Workspaces are the caller's, 16-byte aligned (AIR_EWORKSPACE when too small); nothing
+ * is allocated or synchronised.  All sums are fixed-order partial sums in fp64 - no floating-point atomics: two calls
+ * on one input return the same bits.
+ *
+ * air_pca_gram: mean[d] = the column means of x (N, D) fp32, and gram (D x D fp64, symmetric to the bit) =
+ * sum_n (x[n] - mean)(x[n] - mean)^T - two passes, the centred differences in fp32, products and sums in fp64.  The
+ * host takes the eigenvectors (numpy.linalg.eigh).  air_pca_project: out (N, K) fp32 = (x - mean) comps^T for comps
+ * (K, D) fp32.
+ * air_pairwise_sqdist: out (N, N) fp32 = sum_k (x_i[k] - x_j[k])^2 in feature order - never the expansion
+ * |x_i|^2 + |x_j|^2 - 2 x_i.x_j; the diagonal and equal rows give exactly 0, out[i][j] and out[j][i] the same bits.
+ * air_tsne_affinities: scikit-learn's _binary_search_perplexity over dist (N, N) fp32: cond (N, N) fp32 gets the
+ * conditional probabilities (diagonal 0), beta (N) fp32 each row's precision.  fp64 inside, at most 100 bisection steps,
+ * tolerance 1e-5 nats, a zero row sum replaced by 1e-8.  cond must not alias dist.
+ * air_tsne_joint: P (N, N) in place: max((C + C^T) / max(sum(C + C^T), eps), eps) off the diagonal, 0 on it,
+ * eps = 2.220446049250313e-16 (_joint_probabilities); symmetric to the bit.  ws: air_tsne_ws_bytes(N).
+ *
+ * The descent, one iteration = air_tsne_pairs + air_tsne_update (+ air_tsne_check), all on ws of air_tsne_ws_bytes(N):
+ * air_tsne_pairs: the passes over the pairs of the embedding y (N, 2) fp32, in fp64: Z = sum n_ij,
+ *   n_ij = 1 / (1 + |y_i - y_j|^2), from y alone; then, reading P once (the JOINT distribution: symmetric - row i is
+ *   read as column i), per row and column split the sum of (e p_ij - q_ij) n_ij (y_i - y_j), q_ij = max(n_ij / Z, eps),
+ *   e = exaggeration - _kl_divergence's terms with its floor of q.  want_kl: one more pass for
+ *   sum p log(max(p, eps) / q), p = e p_ij.
+ * air_tsne_gradient: grad (N, 2) fp32 = 4 x the row sums of the last air_tsne_pairs.
+ * air_tsne_update: _gradient_descent's step from the same partials: gains += 0.2 where update * grad < 0, *= 0.8
+ *   elsewhere, floored at 0.01; update = momentum * update - learning_rate * gains * grad; y += update.
+ * air_tsne_check: behind the update of iteration `iter`: writes kl (NaN unless have_kl), grad_norm (of gains * grad, as
+ *   scikit-learn takes it) and n_iter = iter into the status record, and with apply_rules stops the run when the KL
+ *   has not improved for more than n_iter_without_progress iterations or grad_norm <= min_grad_norm.
+ * air_tsne_begin: the start of a _gradient_descent call at iteration iter: update = 0, gains = 1, best error forgotten;
+ *   first != 0 initialises the record too.
+ * Once the record says stopped, pairs / update / check / begin (first = 0) return without touching anything.
+ * air_tsne_run enqueues the whole schedule: begin(first); per iteration i < max_iter: momentum 0.5 and
+ * early_exaggeration while i < exploration_iter, then begin(i) once, momentum 0.8, exaggeration 1 and a check every
+ * n_iter_check iterations; the KL is also taken at the last iteration.  The first phase always runs its full length. */
+typedef struct {
+  int stopped;       /* 0 | 1 */
+  int reason;        /* 0 running / ran to max_iter, 1 no progress, 2 gradient norm */
+  int n_iter;        /* the last iteration a check ran behind (scikit-learn's n_iter_) */
+  int best_iter;
+  double best_error;
+  double kl;
+  double grad_norm;
+  double pad[3];
+} air_tsne_status; /* 64 bytes, device memory */
+typedef struct {
+  int max_iter, exploration_iter, n_iter_check, n_iter_without_progress;
+  float learning_rate, early_exaggeration;
+  double min_grad_norm;
+} air_tsne_schedule;
+int air_vis_max_n(void);              /* 16384 */
+int air_vis_max_d(void);              /* 1024 */
+int air_pca_max_components(void);     /* 16 */
+size_t air_pca_ws_bytes(int N, int D);
+size_t air_tsne_ws_bytes(int N);
+int air_pca_gram(const float* x, int N, int D, float* mean, double* gram, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_pca_project(const float* x, int N, int D, const float* mean, const float* comps, int K, float* out,
+                    air_stream_t stream);
+int air_pairwise_sqdist(const float* x, int N, int D, float* out, air_stream_t stream);
+int air_tsne_affinities(const float* dist, int N, float perplexity, float* cond, float* beta, air_stream_t stream);
+int air_tsne_joint(float* P, int N, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_tsne_begin(float* update, float* gains, int N, int iter, int first, air_tsne_status* status, air_stream_t stream);
+int air_tsne_pairs(const float* P, const float* y, int N, float exaggeration, int want_kl, const air_tsne_status* status,
+                   void* ws, size_t ws_bytes, air_stream_t stream);
+int air_tsne_gradient(int N, float* grad, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_tsne_update(float* y, float* update, float* gains, int N, float momentum, float learning_rate,
+                    const air_tsne_status* status, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_tsne_check(int N, int iter, int have_kl, int apply_rules, int n_iter_without_progress, double min_grad_norm,
+                   air_tsne_status* status, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_tsne_run(const float* P, float* y, float* update, float* gains, int N, const air_tsne_schedule* schedule,
+                 air_tsne_status* status, void* ws, size_t ws_bytes, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

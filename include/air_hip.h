@@ -1204,6 +1204,43 @@ int air_tsne_check(int N, int iter, int have_kl, int apply_rules, int n_iter_wit
 int air_tsne_run(const float* P, float* y, float* update, float* gains, int N, const air_tsne_schedule* schedule,
                  air_tsne_status* status, void* ws, size_t ws_bytes, air_stream_t stream);
 
+/* ---------------------------------------------------------- FLAC decode ----
+ * The waveform read of raw_dataset.py:20-28 (librosa.load / sf.read of a 16 kHz, 16-bit, mono .flac) for a batch of
+ * B files at once, from their compressed audio frames to a ragged (B, Lcap) PCM batch.  The served format is the
+ * fixed-block-size subset of RFC 9639, mono, 16 bit: CONSTANT / VERBATIM / FIXED 0..4 / LPC 1..32 subframes, wasted
+ * bits, RICE and RICE2 residuals of every partition order with escape partitions, every block-size, sample-rate and
+ * frame-number coding, header CRC-8 and frame CRC-16.  The arithmetic is integer: the samples are the encoder's.
+ *
+ * bytes: the audio frames of the B files (metadata stripped) in one buffer of total_bytes, 4-byte aligned.
+ * byte_off (B + 1): row b occupies bytes [(byte_off[b] + 3) & ~3, byte_off[b + 1]) - every row starts 4-byte aligned
+ * and ends at its exact last byte.  lengths (B): samples of row b (STREAMINFO total samples).  blocksize (B): the
+ * row's STREAMINFO block size (every frame but the last has it, the last has it or fewer).
+ * Output: y16 (B, Lcap) int16 and / or y32 (B, Lcap) fp32 = sample / 32768 (exact); at least one is non-NULL.  Samples
+ * [lengths[b], Lcap) of every row are zeroed whatever its status.  status (B) int32: AIR_FLAC_OK or the first reason
+ * row b could not be served; such a row's samples below lengths[b] are unspecified, every other row is unaffected.
+ * Nothing is read outside [0, total_bytes), nothing is written outside the outputs, status and ws, whatever the
+ * bitstream, byte_off, lengths or blocksize hold.
+ *
+ * Frames are located on the device (their lengths are not in their headers): every byte position that carries a
+ * frame header consistent with the row (sync, valid codes, mono, 16 bit, block size <= the row's, CRC-8) is a
+ * candidate; every candidate's bitstream is walked to its end offset and CRC-16; the chain from offset 0 through end
+ * offsets must consist of candidates with matching CRC-16 and frame numbers 0, 1, 2 .., end at the row's last byte
+ * and hold lengths[b] samples.  Only chain frames are decoded, so a sync pattern inside a payload never reaches
+ * the output.  ws: air_flac_workspace_bytes(total_bytes, B) bytes, 16-byte aligned: one bit per byte position plus a
+ * 16-byte record per candidate slot; two candidates are at least 5 bytes apart, the row's slots (a quarter of its
+ * bytes) cannot run out for that reason - a row that would still need more gets AIR_FLAC_CANDIDATE_OVERFLOW. */
+#define AIR_FLAC_OK 0
+#define AIR_FLAC_LOST_SYNC 1          /* the chain of frames breaks, or stops short of the row's last byte */
+#define AIR_FLAC_BAD_CRC16 2          /* a chain frame's CRC-16 does not match */
+#define AIR_FLAC_UNSUPPORTED 3        /* a chain frame outside the served subset (stereo, other sample sizes, reserved
+                                         codes, negative LPC shift, precision code 1111, variable block size) */
+#define AIR_FLAC_LENGTH_MISMATCH 4    /* the chain holds another number of samples than lengths[b] (or > Lcap) */
+#define AIR_FLAC_CANDIDATE_OVERFLOW 5 /* more candidates than the row's record slots */
+size_t air_flac_workspace_bytes(size_t total_bytes, int B);
+int air_flac_decode(const uint8_t* bytes, size_t total_bytes, const int* byte_off, const int* lengths,
+                    const int* blocksize, int B, int Lcap, int16_t* y16_or_null, float* y32_or_null, int* status,
+                    void* ws, size_t ws_bytes, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

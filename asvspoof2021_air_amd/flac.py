@@ -126,16 +126,15 @@ def _pinned_bytes(cap):
     return buf
 
 
-def pack(items, bytes_round=65536):
-    """[(frame bytes uint8, FlacInfo), ...] -> (bytes, byte_off, lengths, blocksize): the rows back to back in one pinned
-    1-D uint8 tensor whose capacity is a multiple of ``bytes_round`` (DevicePrefetcher's ring is keyed by shape: no
-    allocation per batch), every row starting 4-byte aligned.  ``byte_off`` (int32, B + 1): row b occupies
-    ``[(byte_off[b] + 3) & ~3, byte_off[b + 1])`` - byte_off[b + 1] is the exact end of row b (the chain of frames has
-    to end there), the next row starts at the next multiple of 4.  ``lengths`` / ``blocksize`` (int32, B) from STREAMINFO."""
-    if not items:
+def pack_rows(rows, bytes_round=65536):
+    """[uint8 row, ...] -> (bytes, byte_off): the rows back to back in one pinned 1-D uint8 tensor whose capacity is a
+    multiple of ``bytes_round`` (DevicePrefetcher's ring is keyed by shape: no allocation per batch), every row starting
+    4-byte aligned.  ``byte_off`` (int32, B + 1): row b occupies ``[(byte_off[b] + 3) & ~3, byte_off[b + 1])`` -
+    byte_off[b + 1] is the exact end of row b, the next row starts at the next multiple of 4.  (wav.pack shares it.)"""
+    if not rows:
         raise ValueError("pack() needs at least one row")
-    off = np.zeros(len(items) + 1, dtype=np.int64)
-    for b, (row, _) in enumerate(items):
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    for b, row in enumerate(rows):
         off[b + 1] = ((off[b] + 3) & ~3) + int(row.numel())
     used = int(off[-1])
     if used > 2 ** 31 - 1:
@@ -143,14 +142,21 @@ def pack(items, bytes_round=65536):
     cap = max(1, -(-used // int(bytes_round))) * int(bytes_round)
     buf = _pinned_bytes(cap)
     dst = buf.numpy()
-    for b, (row, _) in enumerate(items):
+    for b, row in enumerate(rows):
         s = (int(off[b]) + 3) & ~3
         dst[int(off[b]):s] = 0
         dst[s:int(off[b + 1])] = row.numpy()
     dst[used:] = 0
+    return buf, torch.from_numpy(off.astype(np.int32))
+
+
+def pack(items, bytes_round=65536):
+    """[(frame bytes uint8, FlacInfo), ...] -> (bytes, byte_off, lengths, blocksize): ``pack_rows`` of the rows (the
+    chain of frames has to end at byte_off[b + 1]); ``lengths`` / ``blocksize`` (int32, B) from STREAMINFO."""
+    buf, off = pack_rows([row for row, _ in items], bytes_round)
     lengths = torch.tensor([int(i.total_samples) for _, i in items], dtype=torch.int32)
     blocksize = torch.tensor([int(i.max_blocksize) for _, i in items], dtype=torch.int32)
-    return buf, torch.from_numpy(off.astype(np.int32)), lengths, blocksize
+    return buf, off, lengths, blocksize
 
 
 class FlacDecoder:

@@ -71,6 +71,8 @@ int air_abi_version(void);
  *                         row pieces (8 frames of a channel, transposed into LDS) instead of 2-byte loads down the
  *                         channels; same sums in the same order (air_h_conv1d_tap_pro always does; measured -0.7 % of
  *                         the ECAPA step without a prologue: off)
+ *   RESAMPLE_TABLE_LDS (1) air_resample_ragged / air_wav_decode copy a rate's coefficient table into LDS when it fits
+ *                         (8 / 24 / 32 / 48 kHz -> 16 kHz); 0: every table is read through L2.  Same sums, same order.
  */
 int air_set_option(const char* name, int value);
 int air_get_option(const char* name, int* value_out);
@@ -1240,6 +1242,73 @@ size_t air_flac_workspace_bytes(size_t total_bytes, int B);
 int air_flac_decode(const uint8_t* bytes, size_t total_bytes, const int* byte_off, const int* lengths,
                     const int* blocksize, int B, int Lcap, int16_t* y16_or_null, float* y32_or_null, int* status,
                     void* ws, size_t ws_bytes, air_stream_t stream);
+
+/* ------------------------------------------------- WAV decode / resample ----
+ * The waveform read of raw_dataset.py:20-28 for ``.wav`` files and for anything that is not at the target rate:
+ * librosa.load(path, sr=16000) returns a mono float waveform at 16 kHz whatever the file's rate, channel count or sample
+ * format.  One launch turns a packed batch of WAV payloads (air_wav_decode) or a dense ragged PCM batch
+ * (air_resample_ragged) into the (B, Lcap_out) batch at the target rate; no host synchronisation, no workspace.
+ *
+ * The resampler is defined by its formulas (band-limited sinc interpolation with the parameters of resampy's
+ * 'kaiser_best' filter, every coefficient evaluated exactly at its phase - no table-lookup quantisation):
+ *   Z = 64, R = 0.9475937167399596, BETA = 14.769656459379492
+ *   w(u) = I0(BETA sqrt(1 - (u / Z)^2)) / I0(BETA);  h(u) = R sinc(R u) w(u) for |u| < Z, else 0 (sinc(x) = sin(pi x) / (pi x))
+ *   g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g, s = min(1, L / M), H = ceil(Z / s) (in integers), K = 2 H
+ *   y[t] = sum_{j < K} c[p][j] x[n0 - H + 1 + j],  n0 = floor(t M / L), p = (t M) mod L (64 bit), x = 0 outside [0, n)
+ *   c[p][j] = s h(s (p / L + H - 1 - j)), evaluated in fp64 and rounded once to fp32; n_out = ceil(n L / M).
+ * The device accumulates in fp32: four interleaved ascending fmaf chains (j mod 4), summed (a0 + a1) + (a2 + a3).
+ * sr_in == sr_out is the identity path: L = M = 1, K = 0, no table, no arithmetic beyond the format conversion.
+ *
+ * air_resample_geometry: AIR_EINVAL for a non-positive rate, L > AIR_RESAMPLE_MAX_L or K > AIR_RESAMPLE_MAX_K
+ * (source rates above 16 x the target).  air_resample_table_host fills the L x K table (row p = phase p).  Neither
+ * makes a HIP call.
+ *
+ * desc (host memory, read during the call): nrates <= AIR_RESAMPLE_MAX_RATES records {L, M, K, table_off}; tables
+ * (device, fp32, table_elems values) holds record r's L x K table at table_off.  rate_idx (B, device): the record of
+ * row b.  A desc with nrates outside [1, 8], L / K outside what air_resample_geometry allows, an odd K, an identity
+ * record with K != 0 or a table outside [0, table_elems): AIR_EINVAL, as are NULL pointers, non-positive sizes and, for
+ * air_resample_ragged, an in_kind other than AIR_PCM_S16 / AIR_PCM_F32 - all ahead of any HIP call.
+ *
+ * air_wav_decode: bytes / byte_off as air_flac_decode's (row b occupies [(byte_off[b] + 3) & ~3, byte_off[b + 1]):
+ * the file's ``data`` payload, interleaved little-endian frames).  frames (B): frames of row b.  fmt (B):
+ * AIR_WAV_FMT(kind, bytes per sample, channels).  Conversion to float is what a libsndfile float read returns:
+ * u8 (v - 128) / 128, s16 v / 2^15, s24 v / 2^23, s32 v / 2^31, f32 as is, f64 rounded to fp32; C <= 8 channels are
+ * summed in fp32 in channel order and divided once by C.  air_resample_ragged: x is (B, Lcap_in) int16 or fp32 mono,
+ * lengths (B) its valid samples.
+ * Output: y16 (B, Lcap_out) int16 = saturating round-half-even of 32768 y and / or y32 (B, Lcap_out) fp32 = y, from
+ * the same accumulation; at least one is non-NULL.  Samples [n_out[b], Lcap_out) are zero.  status (B) int32.  A row
+ * whose frames do not fit in its bytes (or lengths[b] > Lcap_in), or whose n_out exceeds Lcap_out:
+ * AIR_WAV_LENGTH_MISMATCH; a format code outside the table above or a rate_idx outside desc: AIR_WAV_BAD_FORMAT.  Such
+ * a row is all zeros; nothing is read outside the row or written outside the outputs; other rows are unaffected. */
+#define AIR_RESAMPLE_MAX_L 640
+#define AIR_RESAMPLE_MAX_K 2048
+#define AIR_RESAMPLE_MAX_RATES 8
+#define AIR_WAV_MAX_CHANNELS 8
+#define AIR_PCM_U8 0
+#define AIR_PCM_S16 1
+#define AIR_PCM_S24 2
+#define AIR_PCM_S32 3
+#define AIR_PCM_F32 4
+#define AIR_PCM_F64 5
+#define AIR_WAV_FMT(kind, bytes, channels) ((kind) | ((bytes) << 4) | ((channels) << 8))
+#define AIR_WAV_OK 0
+#define AIR_WAV_LENGTH_MISMATCH 1
+#define AIR_WAV_BAD_FORMAT 2
+typedef struct {
+  int L, M, K, table_off;
+} air_resample_rate;
+typedef struct {
+  int nrates;
+  air_resample_rate rate[AIR_RESAMPLE_MAX_RATES];
+} air_resample_desc;
+int air_resample_geometry(int sr_in, int sr_out, int* L, int* M, int* K);
+int air_resample_table_host(int sr_in, int sr_out, float* table);
+int air_resample_ragged(const void* x, int in_kind, int B, int Lcap_in, const int* lengths, const int* rate_idx,
+                        const air_resample_desc* desc, const float* tables, size_t table_elems, int16_t* y16_or_null,
+                        float* y32_or_null, int Lcap_out, int* status, air_stream_t stream);
+int air_wav_decode(const uint8_t* bytes, size_t total_bytes, const int* byte_off, const int* frames, const int* fmt,
+                   const int* rate_idx, int B, const air_resample_desc* desc, const float* tables, size_t table_elems,
+                   int16_t* y16_or_null, float* y32_or_null, int Lcap_out, int* status, air_stream_t stream);
 
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight

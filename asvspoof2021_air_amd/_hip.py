@@ -61,6 +61,18 @@ class AirTsneSchedule(ctypes.Structure):
         ("learning_rate", ctypes.c_float), ("early_exaggeration", ctypes.c_float), ("min_grad_norm", ctypes.c_double)]
 
 
+class AirCorpusView(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("lengths", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p), ("tags", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("channels", ctypes.c_void_p), ("n", ctypes.c_int64), ("n_channels", ctypes.c_int),
+                ("elem_bytes", ctypes.c_int)]
+
+
+class AirCorpusSegment(ctypes.Structure):
+    _fields_ = [("perm", ctypes.c_void_p), ("first", ctypes.c_int64), ("count", ctypes.c_int),
+                ("generation", ctypes.c_uint32)]
+
+
 def lib_path():
     return _LIB_PATH
 
@@ -100,7 +112,7 @@ def lib():
                      "air_conv1d_tap_pack_elems", "air_h_bn_ws_bytes", "air_h_conv1d_ws_bytes", "air_conv2d_fwd_stats_bytes", "air_conv2d_dgrad_bn_sums_bytes", "air_conv2d_dgrad_s2_pair_prepack_bytes", "air_h_conv1d_tap_stats_bytes", "air_h_conv1d_tap_bwd_sums_bytes", "air_h_conv1d_pointwise_stats_bytes",
                      "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes", "air_adv_heads_ws_bytes",
                      "air_eval_workspace_bytes", "air_eval_workspace_bytes_grouped", "air_pca_ws_bytes", "air_tsne_ws_bytes",
-                     "air_flac_workspace_bytes"):
+                     "air_flac_workspace_bytes", "air_corpus_permutation_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_size_t
     return _lib

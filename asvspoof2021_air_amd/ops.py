@@ -1349,6 +1349,135 @@ def score_fuse(scores, index=None, weights=None, mode="sum", out=None, n_present
     return out
 
 
+# ---------------------------------------------------------------- device corpus (csrc/corpus.hip)
+CORPUS_ALIGN = 8                # every utterance of a store starts at a multiple of this many elements
+CORPUS_KIND_CROP = 2            # stream = (generation << 2) | kind; kinds 0 and 1: the flows' permutations
+CORPUS_MAX_GENERATION = (1 << 30) - 1
+CORPUS_DTYPES = (torch.int16, torch.float32)
+
+
+def corpus_copy_tile(dtype):
+    """Elements one workgroup of the ragged row copy moves (the tile boundary of air_corpus_copy_rows)."""
+    return int(_hip.lib().air_corpus_copy_tile(ci(torch.empty(0, dtype=dtype).element_size())))
+
+
+def corpus_stream(generation, kind):
+    generation, kind = int(generation), int(kind)
+    if generation < 0 or generation > CORPUS_MAX_GENERATION or kind not in (0, 1, CORPUS_KIND_CROP):
+        raise ValueError("stream of generation %d, kind %d" % (generation, kind))
+    return (generation << 2) | kind
+
+
+def corpus_permutation_ws_bytes(n):
+    return eval_workspace_bytes(n)
+
+
+def corpus_permutation(lo, n, seed, stream_id, out=None, ws=None):
+    """The permutation of [lo, lo + n) that (seed, stream_id) names (air_corpus_permutation), as an int64 (n,) GPU tensor
+    (``out``).  ValueError beyond EVAL_MAX_TRIALS.  Enqueues only; the scratch is ``ws`` (uint8, at least
+    corpus_permutation_ws_bytes(n)) or the stream's workspace."""
+    lo, n = int(lo), int(n)
+    if n < 1 or n > EVAL_MAX_TRIALS:
+        raise ValueError("a permutation takes 1 .. %d elements, got %d" % (EVAL_MAX_TRIALS, n))
+    if lo < 0:
+        raise ValueError("lo must not be negative, got %d" % lo)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device="cuda")
+    elif out.dim() != 1 or out.numel() != n:
+        raise ValueError("out must be int64 of shape (%d,)" % n)
+    L = _hip.lib()
+    need = int(L.air_corpus_permutation_ws_bytes(ci(n)))
+    if ws is None:
+        ws = workspace(need, out.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError("workspace must be a uint8 tensor of >= %d bytes (corpus_permutation_ws_bytes)" % need)
+    _hip.check(L.air_corpus_permutation(ctypes.c_int64(lo), ci(n), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                        ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF), dptr(out, torch.int64),
+                                        dptr(ws, torch.uint8), csz(ws.numel()), stream()), "air_corpus_permutation")
+    return out
+
+
+def corpus_copy_rows(src, dst, lengths, max_len, src_off=None, src_stride=0, dst_off=None, dst_stride=0, dst_cap=0):
+    """air_corpus_copy_rows over 1-d or 2-d GPU tensors of one dtype (int16 | float32): row r moves
+    min(lengths[r], max_len) elements from ``src_off[r]`` (or r * src_stride) to ``dst_off[r]`` (or r * dst_stride);
+    ``dst_cap``: zeros in [length, dst_cap).  ``lengths`` int32, the offsets int64, all on the GPU.  The CALLER vouches
+    that every row lies inside both tensors: the rows' extents are device data."""
+    if src.dtype != dst.dtype or src.dtype not in CORPUS_DTYPES:
+        raise _hip.AirError("corpus rows are int16 or float32 on both sides, got %s -> %s" % (src.dtype, dst.dtype))
+    rows = int(lengths.numel())
+    for off in (src_off, dst_off):
+        if off is not None and off.numel() != rows:
+            raise ValueError("one offset per row")
+    _hip.check(_hip.lib().air_corpus_copy_rows(
+        dptr(src, src.dtype), dptr(src_off, torch.int64, allow_none=True), ctypes.c_int64(int(src_stride)),
+        dptr(dst, dst.dtype), dptr(dst_off, torch.int64, allow_none=True), ctypes.c_int64(int(dst_stride)),
+        dptr(lengths, torch.int32), ci(rows), ci(int(max_len)), ci(int(dst_cap)), ci(src.element_size()), stream()),
+        "air_corpus_copy_rows")
+    return dst
+
+
+def corpus_gather(samples, offsets, lengths, labels, tags, index, channels, n, segments, seed, feat_len, hop, Lcap,
+                  pcm=None):
+    """One batch out of a store (air_corpus_gather).  ``samples``: the flat int16 | float32 store; ``offsets`` (int64),
+    ``lengths`` (int32), ``labels`` / ``tags`` / ``index`` (int64) and ``channels`` ((n, C) int64 or None): its tables,
+    of which the first ``n`` entries are read.  ``segments``: one or two ``(perm, first, count, generation)`` - ``perm``
+    an int64 GPU tensor or None (the identity), of which rows [first, first + count) are drawn.  Returns freshly
+    allocated (pcm (B, Lcap), labels, start, lengths, tags, channels | None, index); ``pcm``: a contiguous (B, Lcap)
+    tensor of the store's dtype to write the samples into instead of a fresh one.  Enqueues only."""
+    if samples.dtype not in CORPUS_DTYPES:
+        raise _hip.AirError("a store is int16 or float32, got %s" % samples.dtype)
+    n, Lcap = int(n), int(Lcap)
+    if Lcap < CORPUS_ALIGN or Lcap % CORPUS_ALIGN:
+        raise ValueError("Lcap must be a positive multiple of %d, got %d" % (CORPUS_ALIGN, Lcap))
+    if not 1 <= len(segments) <= 2:
+        raise ValueError("a batch has one or two segments")
+    for t in (offsets, lengths, labels, tags, index):
+        if t.numel() < n:
+            raise ValueError("a table of the store holds fewer than n = %d entries" % n)
+    C = 0
+    if channels is not None:
+        C = int(channels.shape[1])
+        if channels.dim() != 2 or channels.shape[0] < n or C < 1:
+            raise ValueError("channels must be (>= n, C)")
+    segs = (_hip.AirCorpusSegment * 2)()
+    B = 0
+    for k, (perm, first, count, generation) in enumerate(segments):
+        first, count = int(first), int(count)
+        if count < 0 or first < 0 or first + count > (n if perm is None else perm.numel()):
+            raise ValueError("segment %d draws rows [%d, %d) of %d" % (k, first, first + count,
+                                                                      n if perm is None else perm.numel()))
+        corpus_stream(generation, CORPUS_KIND_CROP)
+        segs[k].perm = perm.data_ptr() if perm is not None else None
+        if perm is not None:
+            dptr(perm, torch.int64)
+        segs[k].first, segs[k].count, segs[k].generation = first, count, int(generation)
+        B += count
+    if B < 1:
+        raise ValueError("an empty batch")
+    dev = samples.device
+    view = _hip.AirCorpusView(samples.data_ptr(), dptr(offsets, torch.int64).value, dptr(lengths, torch.int32).value,
+                              dptr(labels, torch.int64).value, dptr(tags, torch.int64).value,
+                              dptr(index, torch.int64).value,
+                              dptr(channels, torch.int64).value if channels is not None else None, n, C,
+                              samples.element_size())
+    if pcm is None:
+        pcm = torch.empty((B, Lcap), dtype=samples.dtype, device=dev)
+    elif tuple(pcm.shape) != (B, Lcap) or pcm.dtype != samples.dtype:
+        raise ValueError("pcm must be a (%d, %d) %s tensor" % (B, Lcap, samples.dtype))
+    o_len = torch.empty(B, dtype=torch.int32, device=dev)
+    o_start = torch.empty(B, dtype=torch.int32, device=dev)
+    o_lab = torch.empty(B, dtype=torch.int64, device=dev)
+    o_tag = torch.empty(B, dtype=torch.int64, device=dev)
+    o_idx = torch.empty(B, dtype=torch.int64, device=dev)
+    o_ch = torch.empty((B, C), dtype=torch.int64, device=dev) if channels is not None else None
+    _hip.check(_hip.lib().air_corpus_gather(
+        ctypes.byref(view), segs, ci(len(segments)), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ci(int(feat_len)),
+        ci(int(hop)), ci(Lcap), dptr(pcm, pcm.dtype), dptr(o_len, torch.int32), dptr(o_lab, torch.int64),
+        dptr(o_tag, torch.int64), dptr(o_ch, torch.int64, allow_none=True), dptr(o_idx, torch.int64),
+        dptr(o_start, torch.int32), stream()), "air_corpus_gather")
+    return pcm, o_lab, o_start, o_len, o_tag, o_ch, o_idx
+
+
 # ---------------------------------------------------------------- embedding projections (csrc/embed_vis.hip)
 TSNE_STATUS_BYTES = 64  # air_tsne_status
 TSNE_STATUS_DTYPE = [("stopped", "<i4"), ("reason", "<i4"), ("n_iter", "<i4"), ("best_iter", "<i4"),

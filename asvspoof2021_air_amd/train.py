@@ -451,6 +451,27 @@ class Trainer:
                 return out
         return self.step_features(self.features(pcm, start, lengths), labels)
 
+    def train_epoch(self, batches, epoch_num):
+        """The training half of the reference's epoch (main_train.py:287-481) over ``batches`` - an iterable of
+        ``(pcm, labels[, start[, lengths]])``, e.g. ``corpus.CorpusSampler.epoch()`` - without a host synchronisation
+        inside the loop: ``set_epoch``, then per batch ``step`` with the returned loss kept in a device vector.  Behind
+        the loop the losses are fetched in ONE copy and ``train_loss.log`` gets the lines one ``log_step`` per batch
+        would have written, byte for byte.  Returns the per-batch losses as a float32 host array.  The plain trainer
+        only: the ``--ADV_AUG`` columns are log_step's."""
+        from .devbuf import DeviceVector
+        self.set_epoch(epoch_num)
+        losses = DeviceVector(torch.float32, self.device, len(batches) if hasattr(batches, "__len__") else 64)
+        for batch in batches:
+            loss, _ = self.step(batch[0], batch[1], start=batch[2] if len(batch) > 2 else None,
+                                lengths=batch[3] if len(batch) > 3 else None)
+            losses.append(loss)
+        host = losses.view().cpu().numpy()
+        if self.out_fold is not None and air_dist.rank() == 0 and host.size:
+            with open(os.path.join(self.out_fold, "train_loss.log"), "a") as log:
+                # str(float(x)) of the float32 loss: what log_step makes of ``loss.item()``
+                log.write("".join(str(epoch_num) + "\t" + str(i) + "\t" + str(float(v)) + "\n" for i, v in enumerate(host)))
+        return host
+
     # ------------------------------------------------------------------ hipGraph replay
     def enable_graph(self, on=True, segments=None):
         """Capture front-end + forward + loss + backward of one fixed-shape batch in a hipGraph and replay it per

@@ -1310,6 +1310,66 @@ int air_wav_decode(const uint8_t* bytes, size_t total_bytes, const int* byte_off
                    const int* rate_idx, int B, const air_resample_desc* desc, const float* tables, size_t table_elems,
                    int16_t* y16_or_null, float* y32_or_null, int Lcap_out, int* status, air_stream_t stream);
 
+/* -------------------------------------------------------- device corpus ---
+ * The decoded corpus held in HBM and the batch selection of main_train.py:226-345 on the device: a flat store of
+ * utterances (int16 or fp32, every utterance starting at a multiple of 8 elements), a random permutation per flow and
+ * epoch, and one gather per batch that also draws the crop offsets of dataset.py:69.  Nothing here allocates or
+ * synchronises; everything is enqueued on `stream`.
+ *
+ * Random words.  word(i, s) is word 0 of the Philox4x32-10 block with counter {i, s, 0, 0} and key {seed lo, seed hi}
+ * (the generator of air_dropout_mask / air_randn).  s = (generation << 2) | kind: kind 0 and 1 are the permutations of
+ * the first and the second flow, kind 2 the crop offsets.  generation < 2^30.
+ *
+ * air_corpus_permutation: key_i = (uint64)word(i, stream_id) << 32 | i for i < n, padded with all-ones sentinels in the
+ * layout air_eval_sort_keys sorts - the keys are the first npad * 8 bytes of the workspace, npad the power of two
+ * >= max(n, air_eval_sort_block()) - sorted by air_eval_sort_keys itself; perm_out[j] = lo + (key_j & 0xffffffff).  The
+ * keys are distinct, so perm_out is np.sort of the keys exactly.  1 <= n <= air_eval_max_trials() (2^20), more:
+ * AIR_EUNSUPPORTED.  ws: 16-byte aligned, >= air_corpus_permutation_ws_bytes(n) (= air_eval_workspace_bytes(n)) bytes.
+ *
+ * air_corpus_copy_rows: rows ragged rows of elem_bytes (2 | 4) byte elements.  Row r is read at src + src_off[r]
+ * (src_off NULL: r * src_stride) and written at dst + dst_off[r] (dst_off NULL: r * dst_stride), offsets and strides in
+ * elements; min(max(lengths[r], 0), max_len) elements are copied.  dst_cap > 0 (needs dst_off NULL, max_len <= dst_cap
+ * <= dst_stride): the elements [length, dst_cap) of every row are written as zeros.  One workgroup per row and tile of
+ * air_corpus_copy_tile(elem_bytes) elements; a row whose two ends are 16-byte aligned moves 16 bytes per lane, any
+ * other single elements.  The source is never read at or beyond a row's length.  rows <= 65535.
+ *
+ * air_corpus_gather: one batch of B = seg[0].count (+ seg[1].count) rows, those of seg[0] first.  Row r of a segment is
+ * utterance u = perm[first + r] (perm NULL: first + r); a u outside [0, n) yields an empty row.  pcm (B, Lcap) gets the
+ * utterance's samples through the copy above and zeros in [length, Lcap); lengths / labels / tags / index /
+ * channels[b, 0 .. n_channels) the store's entries of u; start[b] the crop offset: T = 1 + length / hop, 0 when
+ * T <= feat_len, else ((uint64)word(u, generation << 2 | 2) * (T - feat_len)) >> 32 - below T - feat_len, the exclusive
+ * bound of np.random.randint(T - feat_len).  Lcap: a multiple of 8 and >= every length drawn (a longer utterance is
+ * cut at Lcap; the caller knows the lengths and refuses it); pcm 16-byte aligned.  channels NULL exactly when the view
+ * has none. */
+typedef struct air_corpus_view {
+  const void* samples;      /* the store, elem_bytes per sample */
+  const int64_t* offsets;   /* n (+ 1) element offsets, each a multiple of 8 */
+  const int* lengths;       /* n */
+  const int64_t* labels;    /* n */
+  const int64_t* tags;      /* n */
+  const int64_t* index;     /* n */
+  const int64_t* channels;  /* (n, n_channels) or NULL */
+  int64_t n;
+  int n_channels;
+  int elem_bytes;           /* 2 | 4 */
+} air_corpus_view;
+typedef struct air_corpus_segment {
+  const int64_t* perm;      /* device, or NULL: the identity */
+  int64_t first;
+  int count;
+  uint32_t generation;      /* of the crop draws */
+} air_corpus_segment;
+int air_corpus_copy_tile(int elem_bytes); /* elements per workgroup tile; 0: unsupported element size */
+size_t air_corpus_permutation_ws_bytes(int n);
+int air_corpus_permutation(int64_t lo, int n, uint64_t seed, uint32_t stream_id, int64_t* perm_out, void* ws,
+                           size_t ws_bytes, air_stream_t stream);
+int air_corpus_copy_rows(const void* src, const int64_t* src_off, int64_t src_stride, void* dst, const int64_t* dst_off,
+                         int64_t dst_stride, const int* lengths, int rows, int max_len, int dst_cap, int elem_bytes,
+                         air_stream_t stream);
+int air_corpus_gather(const air_corpus_view* c, const air_corpus_segment* seg, int nseg, uint64_t seed, int feat_len,
+                      int hop, int Lcap, void* pcm, int* lengths, int64_t* labels, int64_t* tags, int64_t* channels,
+                      int64_t* index, int* start, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

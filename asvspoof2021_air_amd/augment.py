@@ -341,15 +341,17 @@ class AugmentChain:
     """Transmission codec, then recording device - the order of channel_simulation/simulated_device_channel.py:47-54.
     Either stage may be None.  ``prepare(batch)`` draws for the next call and returns what was drawn as the channel
     classes of ``AdversarialTrainer.step(..., channels=)``: 0 = unchanged (the reference's ``no_channel``), index + 1
-    otherwise; (B, 2) int64 (codec, device) with both stages, (B,) with one."""
+    otherwise; (B, 2) int64 (codec, device) with both stages, (B,) with one.  ``waveform`` (a ``RawBoostAugment``), when
+    given, is applied first - it degrades the source signal, ahead of the channel - and adds its own label column in
+    front: 0 = unchanged, index into its ``algos`` + 1."""
 
     supports_lengths = True
 
-    def __init__(self, codec=None, device=None):
-        if codec is None and device is None:
+    def __init__(self, codec=None, device=None, waveform=None):
+        if codec is None and device is None and waveform is None:
             raise ValueError("AugmentChain needs a codec stage, a device stage, or both")
-        self.stages = [s for s in (codec, device) if s is not None]
-        self.codec, self.device = codec, device
+        self.stages = [s for s in (waveform, codec, device) if s is not None]
+        self.codec, self.device, self.waveform = codec, device, waveform
         self._prepared = None
 
     def prepare(self, batch):
@@ -366,3 +368,184 @@ class AugmentChain:
         for k, stage in enumerate(self.stages):
             pcm = stage(pcm, None if drawn is None else drawn[k], lengths=lengths)
         return pcm
+
+
+# ---------------------------------------------------------------------------------------------------------- RawBoost
+# Layout of the parameter table (include/air_hip.h, "RawBoost"): (B, 164) float64, every entry exact in a double.
+RB_HDR, RB_FILTERS, RB_NF, RB_MAXBANDS, RB_MAXTAPS = 8, 6, 5, 8, 512
+RB_FREC = 2 + 3 * RB_MAXBANDS
+RB_ROW = RB_HDR + RB_FILTERS * RB_FREC
+RB_MAXL = 1 << 20                # samples per row the ISD stream reserves; air_rawboost_ragged refuses a longer Lcap
+RB_KEY_TAG = 0x5242 << 36        # Philox keys: RB_KEY_TAG | seed << 1 | {0: ISD, 1: SSI}
+RB_LNL, RB_ISD, RB_SSI = (0, 3, 4, 5, 7), (1, 3, 4, 6, 7), (2, 3, 5, 6)
+RB_DEFAULTS = dict(nBands=5, minF=20.0, maxF=8000.0, minBW=100.0, maxBW=1000.0, minCoeff=10, maxCoeff=100, minG=0.0, maxG=0.0,
+                   minBiasLinNonLin=5.0, maxBiasLinNonLin=20.0, N_f=5, P=10.0, g_sd=2.0, SNRmin=10.0, SNRmax=40.0)
+
+
+def _rb_table(table, B, device):
+    if not (torch.is_tensor(table) and table.is_cuda):
+        raise _hip.AirError("the RawBoost table must be a GPU tensor; there is no CPU fallback")
+    if table.dtype != torch.float64 or tuple(table.shape) != (B, RB_ROW):
+        raise ValueError("the RawBoost table is (%d, %d) float64, got %s %s" % (B, RB_ROW, tuple(table.shape), table.dtype))
+    return table.contiguous()
+
+
+def rawboost_design(table):
+    """table (B, 164) float64 GPU -> (taps (B, 6, 512) fp32, lens (B, 6) int32): the notch cascades ``rawboost`` filters
+    with (``air_rawboost_design``: designed in fp64 on the device, rounded once), zero behind each length."""
+    B = table.shape[0]
+    table = _rb_table(table, B, table.device)
+    taps = torch.empty((B, RB_FILTERS, RB_MAXTAPS), dtype=torch.float32, device=table.device)
+    lens = torch.empty((B, RB_FILTERS), dtype=torch.int32, device=table.device)
+    _hip.check(_hip.lib().air_rawboost_design(_hip.dptr(table, torch.float64), _hip.ci(B), _hip.dptr(taps),
+                                              _hip.dptr(lens, torch.int32), _hip.stream()), "air_rawboost_design")
+    return taps, lens
+
+
+def rawboost(pcm, table, lengths=None, out=None):
+    """pcm (B, L) fp32 or int16 GPU, table (B, 164) float64 GPU (``RawBoostAugment.params``) -> (B, L) fp32: RawBoost
+    (``air_rawboost_ragged``) - per row one of LnL (0), ISD (1), SSI (2), their chains (3 - 6) or the parallel form (7);
+    any other algorithm entry copies the row.  ``lengths`` as in ``ir_convolve``: row b holds lengths[b] samples, its tail
+    is never read and comes back zero, and the row carries the bits of the dense call on that utterance alone."""
+    if not pcm.is_cuda:
+        raise _hip.AirError("rawboost needs GPU tensors; there is no CPU fallback")
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
+    B, L = pcm.shape
+    if L > RB_MAXL:
+        raise ValueError("rows of at most %d samples, got %d" % (RB_MAXL, L))
+    if lengths is not None:
+        lengths = _device_lengths(lengths, B, L, pcm.device)
+    table = _rb_table(table, B, pcm.device)
+    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
+    lib = _hip.lib()
+    n = lib.air_rawboost_ws_bytes(_hip.ci(B), _hip.ci(L))
+    ws = ops.workspace(n, pcm.device)
+    i16 = pcm.dtype == torch.int16
+    null = _hip.dptr(None, allow_none=True)
+    _hip.check(lib.air_rawboost_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
+                                       _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True),
+                                       _hip.dptr(table, torch.float64), _hip.dptr(y), _hip.dptr(ws, torch.uint8), _hip.csz(n),
+                                       _hip.stream()), "air_rawboost_ragged")
+    return y
+
+
+def _upload_table(pinned, table, device):
+    """``_upload_indices`` for the float64 parameter table: pinned staging kept per shape, asynchronous copy."""
+    slot = pinned.get(table.shape)
+    if slot is None:
+        slot = pinned[table.shape] = [torch.empty(table.shape, dtype=torch.float64).pin_memory(), None]
+    if slot[1] is not None:
+        slot[1].synchronize()  # the previous upload from this buffer has executed (one step of run-ahead)
+    slot[0].copy_(torch.from_numpy(table))
+    dev = slot[0].to(device, non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    return dev
+
+
+class RawBoostAugment:
+    """RawBoost (Tak et al., ICASSP 2022), per utterance one algorithm out of ``algos`` (0 LnL, 1 ISD, 2 SSI, 3 all three in
+    series, 4 LnL -> ISD, 5 LnL -> SSI, 6 ISD -> SSI, 7 LnL and ISD in parallel), applied with probability ``p``.
+    ``config`` overrides the authors' defaults (``RB_DEFAULTS``).  A configuration whose cascade could exceed 512 taps,
+    more than 8 bands or more than 5 LnL filters: ValueError.
+
+    One ``np.random.Generator(PCG64(seed))`` serves every draw, each as ``lo + (hi - lo) * rng.random()`` (``U``):
+      ``draw(B)``    ``rng.integers(0, len(algos), B)``, then, with p < 1, ``rng.random(B) >= p`` marks the unchanged rows;
+      ``params(idx)`` rows in order, a row of algorithm a: with LnL, filter i = 0 .. N_f - 1: its nBands bands - fc =
+                     U(minF, maxF), bw = U(minBW, maxBW), c = int(U(minCoeff, maxCoeff)), + 1 if even - then G = U(minG,
+                     maxG) for i = 0 and U(minG - minBias, maxG - maxBias) behind it; with ISD, beta = U(0, P); with SSI,
+                     the bands, G = U(minG, maxG), SNR = U(SNRmin, SNRmax).  Unchanged rows draw nothing.
+    Nothing depends on the rows' lengths.  The Philox counter bases of the two noise stages are held here and advance per
+    ``params`` call by what a batch of B rows of the longest admissible length would use (B 2^20 ISD counters, B 2^18 SSI
+    quads), the two stages under different keys: no two streams of any two calls overlap."""
+
+    supports_lengths = True
+
+    def __init__(self, algos=(0, 1, 2), p=1.0, seed=688, device="cuda", **config):
+        algos = tuple(int(a) for a in algos)
+        if not algos or any(a < 0 or a > 7 for a in algos):
+            raise ValueError("algos must be taken from 0 .. 7, got %s" % (algos,))
+        unknown = sorted(set(config) - set(RB_DEFAULTS))
+        if unknown:
+            raise ValueError("unknown RawBoost parameters: %s" % unknown)
+        cfg = dict(RB_DEFAULTS, **config)
+        cfg["nBands"], cfg["N_f"] = int(cfg["nBands"]), int(cfg["N_f"])
+        if not 1 <= cfg["nBands"] <= RB_MAXBANDS or not 1 <= cfg["N_f"] <= RB_NF:
+            raise ValueError("nBands in [1, %d] and N_f in [1, %d], got %d and %d" % (RB_MAXBANDS, RB_NF, cfg["nBands"], cfg["N_f"]))
+        if not 1 <= cfg["minCoeff"] <= cfg["maxCoeff"]:
+            raise ValueError("1 <= minCoeff <= maxCoeff, got %s and %s" % (cfg["minCoeff"], cfg["maxCoeff"]))
+        c_up = int(cfg["maxCoeff"]) + (1 if int(cfg["maxCoeff"]) % 2 == 0 else 0)
+        if cfg["nBands"] * c_up - (cfg["nBands"] - 1) > RB_MAXTAPS:
+            raise ValueError("%d bands of up to %d coefficients give a cascade of %d taps, above the limit of %d" % (
+                cfg["nBands"], c_up, cfg["nBands"] * c_up - (cfg["nBands"] - 1), RB_MAXTAPS))
+        if not 0 <= int(seed) < 1 << 35:
+            raise ValueError("seed in [0, 2^35), got %s" % seed)
+        self.algos, self.config, self.p, self.seed, self.device = algos, cfg, float(p), int(seed), device
+        self._kernel_algo = np.array(algos, dtype=np.int32)
+        self.rng = np.random.Generator(np.random.PCG64(seed))
+        self.isd_base = self.ssi_base = 0
+        self._pinned = {}
+
+    def draw(self, batch):
+        """(B,) int32 indices into ``algos``, -1 = leave the utterance unchanged."""
+        idx = self.rng.integers(0, len(self.algos), size=batch).astype(np.int32)
+        if self.p < 1.0:
+            idx[self.rng.random(batch) >= self.p] = -1
+        return idx
+
+    def _u(self, lo, hi):
+        return lo + (hi - lo) * self.rng.random()
+
+    def _bands(self):
+        cfg, out = self.config, []
+        for _ in range(cfg["nBands"]):
+            fc, bw = self._u(cfg["minF"], cfg["maxF"]), self._u(cfg["minBW"], cfg["maxBW"])
+            c = int(self._u(cfg["minCoeff"], cfg["maxCoeff"]))
+            out += [fc, bw, c + 1 if c % 2 == 0 else c]
+        return out
+
+    def params(self, idx):
+        """idx (B,) host indices into ``algos`` (-1 unchanged) -> the (B, 164) float64 host table of ``rawboost``."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        B, cfg = idx.size, self.config
+        if self.isd_base + B * RB_MAXL >= 1 << 53:
+            raise OverflowError("the RawBoost noise streams are exhausted: start a new augmenter (another seed)")
+        t = np.zeros((B, RB_ROW), dtype=np.float64)
+        t[:, 0] = np.where(idx < 0, -1, self._kernel_algo[np.clip(idx, 0, len(self.algos) - 1)])
+        t[:, 3], t[:, 4] = self.isd_base, self.ssi_base
+        t[:, 6], t[:, 7] = RB_KEY_TAG | (self.seed << 1), RB_KEY_TAG | (self.seed << 1) | 1
+        for row in t:
+            a = int(row[0])
+            if a in RB_LNL:
+                for i in range(cfg["N_f"]):
+                    rec = row[RB_HDR + i * RB_FREC: RB_HDR + (i + 1) * RB_FREC]
+                    rec[2: 2 + 3 * cfg["nBands"]] = self._bands()
+                    rec[1] = cfg["nBands"]
+                    rec[0] = self._u(cfg["minG"], cfg["maxG"]) if i == 0 else self._u(
+                        cfg["minG"] - cfg["minBiasLinNonLin"], cfg["maxG"] - cfg["maxBiasLinNonLin"])
+            if a in RB_ISD:
+                row[1] = np.floor(self._u(0.0, cfg["P"]) / 100.0 * 4294967296.0)
+                row[2] = cfg["g_sd"]
+            if a in RB_SSI:
+                rec = row[RB_HDR + RB_NF * RB_FREC:]
+                rec[2: 2 + 3 * cfg["nBands"]] = self._bands()
+                rec[1] = cfg["nBands"]
+                rec[0] = self._u(cfg["minG"], cfg["maxG"])
+                row[5] = self._u(cfg["SNRmin"], cfg["SNRmax"])
+        self.isd_base += B * RB_MAXL
+        self.ssi_base += B * (RB_MAXL // 4)
+        return t
+
+    def __call__(self, pcm, idx=None, lengths=None):
+        if pcm.dim() != 2 or pcm.shape[1] > RB_MAXL:
+            raise ValueError("PCM is (B, L) with L <= %d, got %s" % (RB_MAXL, tuple(pcm.shape)))
+        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
+            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
+        if idx is None:
+            idx = self.draw(pcm.shape[0])
+        if torch.is_tensor(idx):
+            idx = idx.cpu().numpy()
+        if len(idx) != pcm.shape[0]:
+            raise ValueError("idx must have %d entries, got %d" % (pcm.shape[0], len(idx)))
+        return rawboost(pcm, _upload_table(self._pinned, self.params(idx), pcm.device), lengths=lengths)

@@ -410,6 +410,56 @@ int air_g711_ragged(const float* x, const int16_t* x16, int B, int Lcap, const i
                     const float* fir, int ntaps, const int* law_idx, int resample, int normalize,
                     float* y, uint8_t* codes_or_null, void* ws, size_t ws_bytes, air_stream_t stream);
 
+/* RawBoost (Tak et al., ICASSP 2022) - the raw-waveform augmentation of the ASVspoof 2021 LA / DF baselines - on a dense
+ * or ragged batch.  Parity with the authors' script and its numpy stream is NOT claimed; this text is the specification.
+ * Rows as in air_g711_ragged: exactly one of x (fp32) / x16 (16-bit PCM, s / 32768), row b holds L_b = clamp(lengths[b],
+ * 1, Lcap) samples, a NULL lengths pointer is the dense batch; y is fp32 (B, Lcap), y[b, L_b:] = 0, nothing at or behind
+ * L_b is read.  fs = 16000.
+ *
+ * The parameter table is DEVICE data, (B, 164) doubles, every entry a value a double holds exactly:
+ *   [0] algorithm: 0 LnL, 1 ISD, 2 SSI, 3 LnL -> ISD -> SSI, 4 LnL -> ISD, 5 LnL -> SSI, 6 ISD -> SSI,
+ *       7 N0(LnL(x) + ISD(x)); anything else copies the row (converted, for x16)
+ *   [1] T = floor(beta / 100 * 2^32), the ISD threshold     [2] g_sd          [5] SNR in dB
+ *   [3] isd_base, [4] ssi_base: the call's Philox counter bases (below)       [6] ISD key, [7] SSI key
+ *   [8 + 26 s ..], s = 0 .. 5, filter slot s: [G in dB, nBands (0: slot unused, at most 8), (fc, bw, c) x 8];
+ *       slots 0 .. 4 are b_0 .. b_4 of the LnL stage (an unused one adds nothing), slot 5 is the SSI filter.
+ *
+ * Notch cascade b = notch(slot) (air_rawboost_design; fp64 on the device, rounded to fp32 once).  Per band, c odd:
+ *   f1 = fc - bw / 2 (1/1000 if <= 0), f2 = fc + bw / 2 (fs/2 - 1/1000 if >= fs/2), l = f1 / (fs/2), r = f2 / (fs/2),
+ *   m = k - (c - 1) / 2, h[k] = (l sinc(l m) + sinc(m) - r sinc(r m)) (0.54 - 0.46 cos(2 pi k / (c - 1))), h /= sum(h)
+ *   - scipy.signal.firwin(c, [f1, f2], window='hamming', fs=fs); b = the linear convolution of the bands' h (sum c -
+ *   (nBands - 1) taps, at most 512), times 10^(G / 20) / max_k |H(k pi / 512)|, k = 0 .. 511.  A slot whose c is even or
+ *   outside [1, 512], or whose cascade exceeds 512 taps, gets no taps (length 0).
+ * Centred FIR: F(b, v)[n] = sum_k b[k] v[n + (len(b) + 1) / 2 - k], n in [0, L_b), v = 0 outside [0, L_b).
+ * Peak rule: N0(y) = y / max|y| if max|y| > 1, else y (an fp32 division by the fp32 peak).
+ *   LnL  y = sum_i F(b_i, p_{i+1}), p_1 = x, p_{j+1} = fl32(p_j x) (fp32, this order); y -= (float) mean(y); N0.
+ *        One fmaf chain per output over all filters' taps (the order of the terms is not part of the specification).
+ *   ISD  sample j is selected iff word 0 of the Philox4x32-10 block at counter isd_base + b Lcap + j, key [6], is < T;
+ *        then y[j] = x[j] + (g x[j]) ((2 u1 - 1) (2 u2 - 1)), u_i = fl32(word i) 2^-32, each operation rounded to
+ *        fp32; else y[j] = x[j]; N0.  (The authors take exactly int(L beta / 100) distinct positions.)
+ *   SSI  n = the standard normals air_randn(seed = key [7], offset = ssi_base + b ceil(Lcap / 4)) would write, element j
+ *        for sample j; q = F(b_5, n); y = fmaf(q, s, x), s = (float)(||x|| / (||q|| 10^(SNR / 20))) from fp64 norms;
+ *        ||q|| = 0 gives y = x.  No peak rule behind it.
+ * Row statistics (sum, max |.|, sum of squares) are per-tile partials in a fixed order, merged in fp64 over the row's
+ * own tiles; no floating-point atomics.  The tiling (air_rawboost_tile() samples, by sample index) depends on the row
+ * alone: a call repeats its bits, and row b carries the bits of the dense call on that utterance alone whose table row
+ * has isd_base + b Lcap and ssi_base + b ceil(Lcap / 4) in [3] and [4].
+ * Random streams: the host holds the two bases and advances them per call - ISD by B 2^20 (Lcap <= 2^20 is enforced, so
+ * a call's counters [isd_base, isd_base + B Lcap) stay inside its reservation), SSI by B 2^18 quads; the two stages use
+ * different keys, so no two streams of any two calls overlap; bases stay below 2^53.
+ * Launches: design (6 B workgroups), LnL FIR, SSI FIR, centre, three pointwise passes - 7, back to back on the stream,
+ * no host synchronisation, so the call can be captured.  air_rawboost_ws_bytes: taps + three (B, Lcap) fp32 buffers +
+ * the partials; 0 for sizes the call refuses.  air_rawboost_design alone writes taps (6 B, 512) fp32 and lens (6 B)
+ * int32, slot s of row b at index 6 b + s - the bits the full call uses.  air_rawboost_row_doubles() = 164.
+ * Both or neither of x / x16, x == y, a NULL y or table, B outside [1, 65535], Lcap outside [1, 2^20]: AIR_EINVAL ahead
+ * of any HIP call; a workspace below air_rawboost_ws_bytes: AIR_EWORKSPACE. */
+int air_rawboost_tile(void);
+int air_rawboost_row_doubles(void);
+size_t air_rawboost_ws_bytes(int B, int Lcap);
+int air_rawboost_design(const double* params, int B, float* taps, int* lens, air_stream_t stream);
+int air_rawboost_ragged(const float* x, const int16_t* x16, int B, int Lcap, const int* lengths_dev_or_null,
+                        const double* params, float* y, void* ws, size_t ws_bytes, air_stream_t stream);
+
 /* --------------------------------------------------------------- conv1d --
  * nn.Conv1d (stride 1) as used by ecapa_tdnn.py:39,46,55,111,118,140,143, with the
  * conv -> ReLU -> BN ordering of ecapa_tdnn.py:67-69 supported by bias / ReLU epilogues.

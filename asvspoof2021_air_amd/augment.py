@@ -10,12 +10,11 @@ files are not distributable with the reference, so ``synthetic_ir_bank`` provide
 (short, coloured) and room-like (exponentially decaying noise tail) responses; a real bank loads
 with ``ChannelAugment(irs=tensor)``.  Arithmetic spec and parity status: oracle/channel.py.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _hip, ops
+from .ragged import PinnedUpload, device_lengths, pcm_pointers
 
 
 def synthetic_ir_bank(n_device=27, n_space=3, taps=1024, sr=16000, seed=688):
@@ -98,20 +97,24 @@ def synthetic_room_bank(n_device=27, n_space=3, sr=16000, seed=688, rt60=(0.2, 1
     return IRBank(rows)
 
 
-def _device_lengths(lengths, B, Lcap, device):
-    """``lengths`` as the int32 (B,) device tensor the ragged kernel reads: a GPU tensor is used as is (the kernel clamps
-    it to [1, Lcap]), a host tensor or sequence is checked (ValueError) and uploaded, as ``LFCC.forward_ragged`` does."""
-    if not (torch.is_tensor(lengths) and lengths.is_cuda):
-        host = torch.as_tensor(lengths).reshape(-1)
-        if host.numel() != B or host.is_floating_point() or host.dtype == torch.bool:
-            raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
-        if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
-            raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
-                Lcap, int(host.min()), int(host.max())))
-        lengths = host.to(torch.int32).to(device)
-    elif lengths.numel() != B:
-        raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
-    return lengths.to(torch.int32).contiguous()  # (no-op for what the dataset hands over)
+def _checked(what, pcm, lengths, out, others=(), dense_fp32=False):
+    """The argument checks of the library entry points here -> (B, L, lengths on the device or None, y): GPU tensors
+    only, PCM float32 or int16 (``dense_fp32``: a dense call's dtype is left to the pointer check), host lengths checked
+    (ValueError) and uploaded, ``out`` or a fresh fp32 result."""
+    if not pcm.is_cuda or any(t is not None and not t.is_cuda for t in others):
+        raise _hip.AirError("%s needs GPU tensors; there is no CPU fallback" % what)
+    if not (dense_fp32 and lengths is None) and pcm.dtype not in (torch.float32, torch.int16):
+        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
+    B, L = pcm.shape
+    if lengths is not None:
+        lengths = device_lengths(lengths, B, L, pcm.device)
+    return B, L, lengths, out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
+
+
+def _call_tail(idx, normalize, y, n):
+    """(idx, normalize, y, workspace, its bytes, stream): what ends the argument lists of the convolution entry points."""
+    return (_hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0), _hip.dptr(y),
+            _hip.dptr(ops.workspace(n, y.device), torch.uint8), _hip.csz(n), _hip.stream())
 
 
 def ir_convolve(pcm, irs, idx=None, normalize=True, out=None, lengths=None):
@@ -126,95 +129,75 @@ def ir_convolve(pcm, irs, idx=None, normalize=True, out=None, lengths=None):
     ``taps`` columns of the response it drew - up to 65 536 of them."""
     if isinstance(irs, IRBank):
         return _bank_convolve(pcm, irs, idx, normalize, out, lengths)
-    if not pcm.is_cuda or not irs.is_cuda:
-        raise _hip.AirError("ir_convolve needs GPU tensors; there is no CPU fallback")
-    B, L = pcm.shape
+    B, L, lengths, y = _checked("ir_convolve", pcm, lengths, out, (irs,), dense_fp32=True)
     n_ir, H = irs.shape
-    if lengths is not None:
-        lengths = _device_lengths(lengths, B, L, pcm.device)
-        if pcm.dtype not in (torch.float32, torch.int16):
-            raise _hip.AirError("a ragged batch is float32 or int16, got %s" % pcm.dtype)
-    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
     lib = _hip.lib()
     n = lib.air_ir_convolve_ws_bytes_ex(_hip.ci(B), _hip.ci(n_ir), _hip.ci(H))  # (+ the FFT tables when H qualifies)
-    ws = ops.workspace(n, pcm.device)
-    tail = (_hip.dptr(irs), _hip.ci(n_ir), _hip.ci(H), _hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0),
-            _hip.dptr(y), _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream())
+    tail = (_hip.dptr(irs), _hip.ci(n_ir), _hip.ci(H)) + _call_tail(idx, normalize, y, n)
     if lengths is None:
         _hip.check(lib.air_ir_convolve(_hip.dptr(pcm), _hip.ci(B), _hip.ci(L), *tail), "air_ir_convolve")
     else:
-        i16 = pcm.dtype == torch.int16
-        null = _hip.dptr(None, allow_none=True)
-        _hip.check(lib.air_ir_convolve_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
-                                              _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32), *tail),
+        _hip.check(lib.air_ir_convolve_ragged(*pcm_pointers(pcm), _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32), *tail),
                    "air_ir_convolve_ragged")
     return y
 
 
 def _bank_convolve(pcm, bank, idx, normalize, out, lengths):
-    if not pcm.is_cuda or not bank.irs.is_cuda or not bank.taps.is_cuda:
-        raise _hip.AirError("ir_convolve needs GPU tensors; there is no CPU fallback")
-    if pcm.dtype not in (torch.float32, torch.int16):
-        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
-    B, L = pcm.shape
+    B, L, lengths, y = _checked("ir_convolve", pcm, lengths, out, (bank.irs, bank.taps))
     n_ir, H = bank.irs.shape
-    if lengths is not None:
-        lengths = _device_lengths(lengths, B, L, pcm.device)
-    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
     lib = _hip.lib()
     n = lib.air_ir_bank_ws_bytes(_hip.ci(B), _hip.ci(L), _hip.ci(n_ir), _hip.ci(H))
-    ws = ops.workspace(n, pcm.device)
-    i16 = pcm.dtype == torch.int16
-    null = _hip.dptr(None, allow_none=True)
-    _hip.check(lib.air_ir_bank_convolve(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
-                                        _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True), _hip.dptr(bank.irs),
-                                        _hip.ci(n_ir), _hip.ci(H), _hip.dptr(bank.taps, torch.int32),
-                                        _hip.dptr(idx, torch.int32, True), _hip.ci(1 if normalize else 0), _hip.dptr(y),
-                                        _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream()), "air_ir_bank_convolve")
+    _hip.check(lib.air_ir_bank_convolve(*pcm_pointers(pcm), _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True),
+                                        _hip.dptr(bank.irs), _hip.ci(n_ir), _hip.ci(H), _hip.dptr(bank.taps, torch.int32),
+                                        *_call_tail(idx, normalize, y, n)), "air_ir_bank_convolve")
     return y
 
 
-class ChannelAugment:
-    """Per-utterance random IR from a bank - a (n_ir, H) tensor or an ``IRBank`` - applied with probability ``p``."""
+class _RandomAugment:
+    """What the augmenters share: per utterance one of ``len(getattr(self, CHOICES))`` choices, applied with probability
+    ``p``, drawn from one ``np.random.Generator(PCG64(seed))``; host arrays go up through ``self._upload``."""
 
     supports_lengths = True  # __call__(pcm, lengths=...) augments a ragged batch over each row's own samples (Trainer.step)
+    CHOICES = None           # the attribute that holds the choices: "irs" | "laws" | "algos"
 
-    def __init__(self, irs=None, p=1.0, seed=688, normalize=True, device="cuda"):
-        if isinstance(irs, IRBank):
-            self.irs = irs.to(device)
-        else:
-            self.irs = (irs if irs is not None else synthetic_ir_bank()).to(device=device, dtype=torch.float32).contiguous()
+    def __init__(self, p, seed):
         self.p = float(p)
-        self.normalize = normalize
         self.rng = np.random.Generator(np.random.PCG64(seed))
-        self._pinned = {}  # batch size -> pinned host staging buffer for the index upload
+        self._upload = PinnedUpload()
 
     def draw(self, batch):
-        """(B,) int32 IR indices, -1 = leave the utterance unchanged."""
-        idx = self.rng.integers(0, len(self.irs), size=batch).astype(np.int32)
+        """(B,) int32 indices into the choices, -1 = leave the utterance unchanged."""
+        idx = self.rng.integers(0, len(getattr(self, self.CHOICES)), size=batch).astype(np.int32)
         if self.p < 1.0:
             idx[self.rng.random(batch) >= self.p] = -1
         return idx
 
+    def _begin(self, pcm, idx, lengths):
+        """The head of every ``__call__`` -> (idx, lengths on the device): the lengths are checked ahead of the draw - a
+        refused batch must not advance the generator."""
+        if lengths is not None:
+            lengths = device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
+        return (self.draw(pcm.shape[0]) if idx is None else idx), lengths
+
+
+class ChannelAugment(_RandomAugment):
+    """Per-utterance random IR from a bank - a (n_ir, H) tensor or an ``IRBank`` - applied with probability ``p``."""
+
+    CHOICES = "irs"
+
+    def __init__(self, irs=None, p=1.0, seed=688, normalize=True, device="cuda"):
+        super().__init__(p, seed)
+        if isinstance(irs, IRBank):
+            self.irs = irs.to(device)
+        else:
+            self.irs = (irs if irs is not None else synthetic_ir_bank()).to(device=device, dtype=torch.float32).contiguous()
+        self.normalize = normalize
+
     def __call__(self, pcm, idx=None, lengths=None):
         """``lengths``: int32 (B,), a ragged batch (``ir_convolve``): fp32 or int16 in, fp32 out, the rows' tails zero."""
-        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
-            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
-        if idx is None:
-            idx = self.draw(pcm.shape[0])
+        idx, lengths = self._begin(pcm, idx, lengths)
         if not torch.is_tensor(idx):
-            # asynchronous upload from a pinned buffer: a pageable .to(device) would synchronise the
-            # stream and drain the step's launch queue (measured: ~1 ms per step)
-            idx = np.asarray(idx, dtype=np.int32)
-            slot = self._pinned.get(idx.size)
-            if slot is None:
-                slot = self._pinned[idx.size] = [torch.empty(idx.size, dtype=torch.int32).pin_memory(), None]
-            if slot[1] is not None:
-                slot[1].synchronize()  # the previous upload from this buffer has executed (one step of run-ahead)
-            slot[0].copy_(torch.from_numpy(idx))
-            idx = slot[0].to(pcm.device, non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record()
+            idx = self._upload(np.asarray(idx, dtype=np.int32), pcm.device)
         return ir_convolve(pcm, self.irs, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), self.normalize,
                            lengths=lengths)
 
@@ -246,26 +229,16 @@ def g711_codec(pcm, law_idx=None, lengths=None, fir=None, resample=True, normali
     ``lengths`` as in ``ir_convolve``: row b holds lengths[b] samples, its tail is never read and comes back zero.
     ``fir``: the low-pass (odd, at most 127 taps; default ``codec_lowpass()``).  ``resample=False`` codes every sample
     at its own rate.  ``return_codes``: also the uint8 codes, (B, (L + 1) // 2) or, without resampling, (B, L)."""
-    if not pcm.is_cuda or (fir is not None and not fir.is_cuda) or (law_idx is not None and not law_idx.is_cuda):
-        raise _hip.AirError("g711_codec needs GPU tensors; there is no CPU fallback")
-    if pcm.dtype not in (torch.float32, torch.int16):
-        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
-    B, L = pcm.shape
-    if lengths is not None:
-        lengths = _device_lengths(lengths, B, L, pcm.device)
+    B, L, lengths, y = _checked("g711_codec", pcm, lengths, out, (fir, law_idx))
     if law_idx is not None and law_idx.numel() != B:
         raise ValueError("law_idx must have %d entries, got %d" % (B, law_idx.numel()))
     if fir is None:
         fir = _default_fir(pcm.device)
-    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
     codes = torch.empty((B, (L + 1) // 2 if resample else L), dtype=torch.uint8, device=pcm.device) if return_codes else None
     lib = _hip.lib()
     n = lib.air_g711_ws_bytes(_hip.ci(B))
     ws = ops.workspace(n, pcm.device)
-    i16 = pcm.dtype == torch.int16
-    null = _hip.dptr(None, allow_none=True)
-    _hip.check(lib.air_g711_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
-                                   _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True), _hip.dptr(fir),
+    _hip.check(lib.air_g711_ragged(*pcm_pointers(pcm), _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True), _hip.dptr(fir),
                                    _hip.ci(fir.numel()), _hip.dptr(law_idx, torch.int32, True), _hip.ci(1 if resample else 0),
                                    _hip.ci(1 if normalize else 0), _hip.dptr(y), _hip.dptr(codes, torch.uint8, True),
                                    _hip.dptr(ws, torch.uint8), _hip.csz(n), _hip.stream()), "air_g711_ragged")
@@ -282,59 +255,31 @@ def _default_fir(device):
     return _FIR[key]
 
 
-class CodecAugment:
+class CodecAugment(_RandomAugment):
     """Per-utterance random G.711 law out of ``laws``, applied with probability ``p`` (the sample-parallel entries of the
     reference's ``codec_landline`` list; channel_simulation/simulated_channel.py degrades the corpus with them offline)."""
 
-    supports_lengths = True
+    CHOICES = "laws"
 
     def __init__(self, laws=("ulaw", "alaw"), p=1.0, seed=688, normalize=True, fir=None, device="cuda"):
         if not laws or any(name not in LAWS for name in laws):
             raise ValueError("laws must be taken from %s, got %s" % (LAWS, laws))
+        super().__init__(p, seed)
         self.laws = tuple(laws)
         self._kernel_law = np.array([LAWS.index(name) for name in self.laws], dtype=np.int32)
-        self.p = float(p)
         self.normalize = normalize
         self.device = device
         self.fir = None if fir is None else fir.to(device=device, dtype=torch.float32).contiguous()
-        self.rng = np.random.Generator(np.random.PCG64(seed))
-        self._pinned = {}
-
-    def draw(self, batch):
-        """(B,) int32 indices into ``laws``, -1 = leave the utterance unchanged."""
-        idx = self.rng.integers(0, len(self.laws), size=batch).astype(np.int32)
-        if self.p < 1.0:
-            idx[self.rng.random(batch) >= self.p] = -1
-        return idx
 
     def __call__(self, pcm, idx=None, lengths=None):
-        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
-            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
-        if idx is None:
-            idx = self.draw(pcm.shape[0])
+        idx, lengths = self._begin(pcm, idx, lengths)
         if not torch.is_tensor(idx):
             idx = np.asarray(idx, dtype=np.int32)
-            idx = _upload_indices(self._pinned, np.where(idx < 0, -1, self._kernel_law[np.maximum(idx, 0)]).astype(np.int32),
-                                  pcm.device)
+            idx = self._upload(np.where(idx < 0, -1, self._kernel_law[np.maximum(idx, 0)]).astype(np.int32), pcm.device)
         elif self.laws != LAWS:
             raise ValueError("device indices are the kernel's own (0 mu-law, 1 A-law): pass host indices with laws=%s" % (self.laws,))
         return g711_codec(pcm, idx.to(device=pcm.device, dtype=torch.int32).contiguous(), lengths=lengths, fir=self.fir,
                           normalize=self.normalize)
-
-
-def _upload_indices(pinned, idx, device):
-    """Asynchronous upload of a host int32 array from a pinned buffer kept per batch size (as ``ChannelAugment.__call__``:
-    a pageable copy would synchronise the stream)."""
-    slot = pinned.get(idx.size)
-    if slot is None:
-        slot = pinned[idx.size] = [torch.empty(idx.size, dtype=torch.int32).pin_memory(), None]
-    if slot[1] is not None:
-        slot[1].synchronize()  # the previous upload from this buffer has executed (one step of run-ahead)
-    slot[0].copy_(torch.from_numpy(idx))
-    dev = slot[0].to(device, non_blocking=True)
-    slot[1] = torch.cuda.Event()
-    slot[1].record()
-    return dev
 
 
 class AugmentChain:
@@ -361,7 +306,7 @@ class AugmentChain:
 
     def __call__(self, pcm, lengths=None):
         if lengths is not None:  # ahead of any draw
-            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
+            lengths = device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
         drawn, self._prepared = self._prepared, None
         if drawn is not None and len(drawn[0]) != pcm.shape[0]:
             raise ValueError("prepared for a batch of %d, called with %d" % (len(drawn[0]), pcm.shape[0]))
@@ -407,44 +352,20 @@ def rawboost(pcm, table, lengths=None, out=None):
     (``air_rawboost_ragged``) - per row one of LnL (0), ISD (1), SSI (2), their chains (3 - 6) or the parallel form (7);
     any other algorithm entry copies the row.  ``lengths`` as in ``ir_convolve``: row b holds lengths[b] samples, its tail
     is never read and comes back zero, and the row carries the bits of the dense call on that utterance alone."""
-    if not pcm.is_cuda:
-        raise _hip.AirError("rawboost needs GPU tensors; there is no CPU fallback")
-    if pcm.dtype not in (torch.float32, torch.int16):
-        raise _hip.AirError("PCM is float32 or int16, got %s" % pcm.dtype)
-    B, L = pcm.shape
+    B, L, lengths, y = _checked("rawboost", pcm, lengths, out)
     if L > RB_MAXL:
         raise ValueError("rows of at most %d samples, got %d" % (RB_MAXL, L))
-    if lengths is not None:
-        lengths = _device_lengths(lengths, B, L, pcm.device)
     table = _rb_table(table, B, pcm.device)
-    y = out if out is not None else torch.empty(pcm.shape, dtype=torch.float32, device=pcm.device)
     lib = _hip.lib()
     n = lib.air_rawboost_ws_bytes(_hip.ci(B), _hip.ci(L))
     ws = ops.workspace(n, pcm.device)
-    i16 = pcm.dtype == torch.int16
-    null = _hip.dptr(None, allow_none=True)
-    _hip.check(lib.air_rawboost_ragged(null if i16 else _hip.dptr(pcm), _hip.dptr(pcm, torch.int16) if i16 else null,
-                                       _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True),
+    _hip.check(lib.air_rawboost_ragged(*pcm_pointers(pcm), _hip.ci(B), _hip.ci(L), _hip.dptr(lengths, torch.int32, True),
                                        _hip.dptr(table, torch.float64), _hip.dptr(y), _hip.dptr(ws, torch.uint8), _hip.csz(n),
                                        _hip.stream()), "air_rawboost_ragged")
     return y
 
 
-def _upload_table(pinned, table, device):
-    """``_upload_indices`` for the float64 parameter table: pinned staging kept per shape, asynchronous copy."""
-    slot = pinned.get(table.shape)
-    if slot is None:
-        slot = pinned[table.shape] = [torch.empty(table.shape, dtype=torch.float64).pin_memory(), None]
-    if slot[1] is not None:
-        slot[1].synchronize()  # the previous upload from this buffer has executed (one step of run-ahead)
-    slot[0].copy_(torch.from_numpy(table))
-    dev = slot[0].to(device, non_blocking=True)
-    slot[1] = torch.cuda.Event()
-    slot[1].record()
-    return dev
-
-
-class RawBoostAugment:
+class RawBoostAugment(_RandomAugment):
     """RawBoost (Tak et al., ICASSP 2022), per utterance one algorithm out of ``algos`` (0 LnL, 1 ISD, 2 SSI, 3 all three in
     series, 4 LnL -> ISD, 5 LnL -> SSI, 6 ISD -> SSI, 7 LnL and ISD in parallel), applied with probability ``p``.
     ``config`` overrides the authors' defaults (``RB_DEFAULTS``).  A configuration whose cascade could exceed 512 taps,
@@ -460,7 +381,7 @@ class RawBoostAugment:
     ``params`` call by what a batch of B rows of the longest admissible length would use (B 2^20 ISD counters, B 2^18 SSI
     quads), the two stages under different keys: no two streams of any two calls overlap."""
 
-    supports_lengths = True
+    CHOICES = "algos"
 
     def __init__(self, algos=(0, 1, 2), p=1.0, seed=688, device="cuda", **config):
         algos = tuple(int(a) for a in algos)
@@ -481,18 +402,10 @@ class RawBoostAugment:
                 cfg["nBands"], c_up, cfg["nBands"] * c_up - (cfg["nBands"] - 1), RB_MAXTAPS))
         if not 0 <= int(seed) < 1 << 35:
             raise ValueError("seed in [0, 2^35), got %s" % seed)
-        self.algos, self.config, self.p, self.seed, self.device = algos, cfg, float(p), int(seed), device
+        super().__init__(p, seed)
+        self.algos, self.config, self.seed, self.device = algos, cfg, int(seed), device
         self._kernel_algo = np.array(algos, dtype=np.int32)
-        self.rng = np.random.Generator(np.random.PCG64(seed))
         self.isd_base = self.ssi_base = 0
-        self._pinned = {}
-
-    def draw(self, batch):
-        """(B,) int32 indices into ``algos``, -1 = leave the utterance unchanged."""
-        idx = self.rng.integers(0, len(self.algos), size=batch).astype(np.int32)
-        if self.p < 1.0:
-            idx[self.rng.random(batch) >= self.p] = -1
-        return idx
 
     def _u(self, lo, hi):
         return lo + (hi - lo) * self.rng.random()
@@ -540,12 +453,9 @@ class RawBoostAugment:
     def __call__(self, pcm, idx=None, lengths=None):
         if pcm.dim() != 2 or pcm.shape[1] > RB_MAXL:
             raise ValueError("PCM is (B, L) with L <= %d, got %s" % (RB_MAXL, tuple(pcm.shape)))
-        if lengths is not None:  # checked ahead of the draw: a refused batch must not advance the generator
-            lengths = _device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device)
-        if idx is None:
-            idx = self.draw(pcm.shape[0])
+        idx, lengths = self._begin(pcm, idx, lengths)
         if torch.is_tensor(idx):
             idx = idx.cpu().numpy()
         if len(idx) != pcm.shape[0]:
             raise ValueError("idx must have %d entries, got %d" % (pcm.shape[0], len(idx)))
-        return rawboost(pcm, _upload_table(self._pinned, self.params(idx), pcm.device), lengths=lengths)
+        return rawboost(pcm, self._upload(self.params(idx), pcm.device), lengths=lengths)

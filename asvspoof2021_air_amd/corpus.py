@@ -22,8 +22,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .ragged import RAGGED_ROUND, PinnedUpload, round_capacity  # noqa: F401  (RAGGED_ROUND: re-exported)
 
-RAGGED_ROUND = 16000            # default Lcap: the longest utterance rounded up to this (dataset._collate_ragged)
 MAX_PERMUTATION = 1 << 20       # air_eval_max_trials(): the longest range one flow permutes
 
 DeviceBatch = collections.namedtuple("DeviceBatch", ("pcm", "labels", "start", "lengths", "tags", "channels", "index"))
@@ -129,7 +129,7 @@ def resolve_lcap(Lcap, lengths, ranges):
     lengths = np.asarray(lengths)
     longest = max(int(lengths[lo:hi].max()) for lo, hi in ranges)
     if Lcap is None:
-        return _round_up(longest, RAGGED_ROUND)
+        return round_capacity(longest)
     Lcap = int(Lcap)
     if Lcap < ops.CORPUS_ALIGN or Lcap % ops.CORPUS_ALIGN:
         raise ValueError("Lcap must be a positive multiple of %d, got %d" % (ops.CORPUS_ALIGN, Lcap))
@@ -160,6 +160,7 @@ class DeviceCorpus:
         self._tables = None            # name -> tensor of capacity ``_ucap`` rows (offsets: + 1)
         self._ucap = 0
         self.n_channels = None         # fixed by the first append: 0 = none
+        self._upload = PinnedUpload()
 
     # -- views
     def __len__(self):
@@ -270,10 +271,7 @@ class DeviceCorpus:
         self._reserve_samples(int(pos[B]))
         self._reserve_utterances(first + B)
         # one pinned upload for what the host computed: [offsets (B + 1) | lengths (B) | index (B)]
-        pack = torch.empty(3 * B + 1, dtype=torch.int64, pin_memory=True)
-        host = pack.numpy()
-        host[:B + 1], host[B + 1:2 * B + 1], host[2 * B + 1:] = pos, lens, np.arange(first, first + B)
-        pack = pack.to(dev, non_blocking=True)
+        pack = self._upload(np.concatenate((pos, lens, np.arange(first, first + B, dtype=np.int64))), dev)
         t = self._tables
         t["offsets"][first:first + B + 1].copy_(pack[:B + 1])
         t["lengths"][first:first + B].copy_(pack[B + 1:2 * B + 1])

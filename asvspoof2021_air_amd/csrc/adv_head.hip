@@ -5,22 +5,11 @@
 #include <cstdint>
 
 #include "air_common.h"
+#include "air_philox.h"
 
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0];
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-  k[0] += 0x9E3779B9u;
-  k[1] += 0xBB67AE85u;
-}
 
 // nn.Dropout(p) keep-mask, already scaled: keep = (u >= p) / (1 - p), u ~ U[0,1) from Philox4x32-10.  One body for
 // the host-offset draw, the device-counter draw (air_dropout_mask_ctr) and the draw inside the fused heads
@@ -28,14 +17,11 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2])
 __device__ __forceinline__ void dropout_quad(float* keep, size_t n, float p, uint64_t seed, uint64_t offset,
                                              size_t quad) {
   if (quad * 4 >= n) return;
-  const uint64_t ctr = offset + quad;
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) philox_round(c, k);
+  uint32_t c[4];
+  air_philox_block(offset + quad, seed, c);
   const float scale = 1.0f / (1.0f - p);
   for (int j = 0; j < 4; ++j)
-    if (quad * 4 + j < n) keep[quad * 4 + j] = ((float)c[j] * 2.3283064365386963e-10f >= p) ? scale : 0.0f;
+    if (quad * 4 + j < n) keep[quad * 4 + j] = (air_philox_u01(c[j]) >= p) ? scale : 0.0f;
 }
 __device__ __forceinline__ void dropout_body(float* __restrict__ keep, size_t n, float p, uint64_t seed,
                                              uint64_t offset) {

@@ -42,6 +42,7 @@
 #include "air_common.h"
 #include "air_fft16.h"
 #include "air_options.h"
+#include "air_pcm.h"
 #include "g711.h"
 
 namespace {
@@ -50,23 +51,11 @@ constexpr int FIR_NT = 256, FIR_R = 8, FIR_BLK = FIR_NT * FIR_R, FIR_KC = 1024;
 constexpr int FIR_GROUPS = (FIR_BLK + FIR_KC) / 8;  // 384 groups of 8 samples per staged segment
 constexpr int FIR_GS = 12;                           // floats per group slot (8 data + 4 pad)
 
-__device__ __forceinline__ void atomic_max_pos(unsigned* p, float v) {
-  atomicMax(p, __float_as_uint(v));  // v >= 0: unsigned order == float order
-}
-
-__device__ __forceinline__ float ir_sample(const float* __restrict__ p, int i) { return p[i]; }
-__device__ __forceinline__ float ir_sample(const short* __restrict__ p, int i) { return (float)p[i] * (1.0f / 32768.0f); }  // exact
-
-// samples of row b: its length from device memory, kept inside the row (ragged), or the whole row (lengths NULL)
-__device__ __forceinline__ int ir_row_len(const int* __restrict__ lengths, int b, int Lcap) {
-  return lengths ? min(max(lengths[b], 1), Lcap) : Lcap;
-}
-
 // y[n0 + i] = x[n0 + i] for n0 + i < L, 0 up to Lcap (i < span): pass-through rows, and with n0 >= L the dead tail
 template <typename T>
 __device__ __forceinline__ void ir_copy_span(const T* __restrict__ xb, float* __restrict__ yb, int n0, int span, int L, int Lcap,
                                              int t, int nt) {
-  for (int n = n0 + t; n < min(n0 + span, Lcap); n += nt) yb[n] = n < L ? ir_sample(xb, n) : 0.0f;
+  for (int n = n0 + t; n < min(n0 + span, Lcap); n += nt) yb[n] = n < L ? air_pcm_sample(xb, n) : 0.0f;
 }
 
 template <typename T>
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(FIR_NT) void fir_kernel(const T* __restrict__ x, in
   __shared__ __attribute__((aligned(16))) float xs[FIR_GROUPS * FIR_GS];
   __shared__ __attribute__((aligned(16))) float hs[FIR_KC];
   const int b = blockIdx.y, n0 = blockIdx.x * FIR_BLK, t = threadIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   float* __restrict__ yb = y + (size_t)b * Lcap;
   const int ir = idx ? min(idx[b], n_ir - 1) : 0;  // indices are caller data: never read past the IR table
@@ -97,7 +86,7 @@ __global__ __launch_bounds__(FIR_NT) void fir_kernel(const T* __restrict__ x, in
     const int m0 = n0 - kc - (FIR_KC - 1);
     for (int p = t; p < FIR_GROUPS * 8; p += FIR_NT) {
       const int m = m0 + p;
-      const float v = (m >= 0 && m < L) ? ir_sample(xb, m) : 0.0f;
+      const float v = (m >= 0 && m < L) ? air_pcm_sample(xb, m) : 0.0f;
       xs[(p >> 3) * FIR_GS + (p & 7)] = v;
       if (kc == 0 && p >= FIR_KC - 1) xpeak = fmaxf(xpeak, fabsf(v));  // this block's own samples
     }
@@ -160,7 +149,7 @@ __global__ __launch_bounds__(256) void fir_rescale_kernel(float* __restrict__ y,
   const float px = __uint_as_float(peaks[2 * b]), py = __uint_as_float(peaks[2 * b + 1]);
   if (!(py > 0.0f)) return;
   const float g = px / py;
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   float* __restrict__ yb = y + (size_t)b * Lcap;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < L; i += gridDim.x * 256) yb[i] *= g;
 }
@@ -274,8 +263,8 @@ __device__ __forceinline__ void fc_convolve_pair(const T* __restrict__ xb, float
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int mA = baseA - FC_OV + 256 * j + t, mB = mA + FC_V;
-    const float a = (mA >= 0 && mA < L) ? ir_sample(xb, mA) : 0.0f;
-    const float c = mB < L ? ir_sample(xb, mB) : 0.0f;
+    const float a = (mA >= 0 && mA < L) ? air_pcm_sample(xb, mA) : 0.0f;
+    const float c = mB < L ? air_pcm_sample(xb, mB) : 0.0f;
     v[j] = cf{a, c};
     if (j >= FC_OV / 256) xpeak = fmaxf(xpeak, fmaxf(fabsf(a), fabsf(c)));  // the blocks' own samples
   }
@@ -318,7 +307,7 @@ __global__ __launch_bounds__(FC_NT) void fc_convolve_kernel(const T* __restrict_
                                                             unsigned* __restrict__ peaks, int n_ir) {
   __shared__ cf buf[FC_LDS];
   const int b = blockIdx.y, t = threadIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   float* __restrict__ yb = y + (size_t)b * Lcap;
   const int ir = idx ? min(idx[b], n_ir - 1) : 0;
@@ -440,7 +429,7 @@ __global__ __launch_bounds__(GC_NT) void g711_resample_kernel(const T* __restric
   __shared__ float hs[GC_MAXTAPS + 1];
   __shared__ float dec[256];
   const int b = blockIdx.y, n0 = blockIdx.x * GC_T, t = threadIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap), M = (L + 1) >> 1, Mcap = (Lcap + 1) >> 1;
+  const int L = air_row_len(lengths, b, Lcap), M = (L + 1) >> 1, Mcap = (Lcap + 1) >> 1;
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   float* __restrict__ yb = y + (size_t)b * Lcap;
   unsigned char* __restrict__ cb = codes ? codes + (size_t)b * Mcap : nullptr;
@@ -457,7 +446,7 @@ __global__ __launch_bounds__(GC_NT) void g711_resample_kernel(const T* __restric
   float xpeak = 0.0f;
   for (int p = t; p < min(2 * GC_XH, GC_T + 4 * c + 12); p += GC_NT) {
     const int i = ib + p;
-    const float v = (i >= 0 && i < L) ? ir_sample(xb, i) : 0.0f;
+    const float v = (i >= 0 && i < L) ? air_pcm_sample(xb, i) : 0.0f;
     xs[(p & 1) * GC_XH + (p >> 1)] = v;
     if (i >= n0 && i < n0 + GC_T) xpeak = fmaxf(xpeak, fabsf(v));  // this tile's own samples
   }
@@ -534,7 +523,7 @@ __global__ __launch_bounds__(GC_NT) void g711_code_kernel(const T* __restrict__ 
                                                           const int* __restrict__ law_idx, float* __restrict__ y,
                                                           unsigned char* __restrict__ codes, unsigned* __restrict__ peaks) {
   const int b = blockIdx.y, n0 = blockIdx.x * GC_T, t = threadIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   float* __restrict__ yb = y + (size_t)b * Lcap;
   unsigned char* __restrict__ cb = codes ? codes + (size_t)b * Lcap : nullptr;
@@ -548,7 +537,7 @@ __global__ __launch_bounds__(GC_NT) void g711_code_kernel(const T* __restrict__ 
     float v = 0.0f;
     int code = 0;
     if (n < L) {
-      const float s = ir_sample(xb, n);
+      const float s = air_pcm_sample(xb, n);
       code = g711_encode(law, g711_quantise(s));
       v = (float)g711_decode(law, code) * (1.0f / 32768.0f);
       xpeak = fmaxf(xpeak, fabsf(s));
@@ -652,7 +641,7 @@ __global__ __launch_bounds__(FC_NT) void pb_forward_kernel(const T* __restrict__
   if (ir < 0) return;
   const int taps = pb_taps(ir_taps, ir, Hmax);
   if (taps <= FC_MAXH || (odd && taps <= PB_P)) return;  // the short form; a row without an odd partition
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   if (2 * m * PB_P >= L) return;  // no pair of output blocks of this row reaches back to m
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   const int s0 = (2 * m - odd - 1) * PB_P;  // first sample of the real part's segment; the imaginary part's is PB_P further
@@ -661,8 +650,8 @@ __global__ __launch_bounds__(FC_NT) void pb_forward_kernel(const T* __restrict__
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int mA = s0 + 256 * j + t, mB = mA + PB_P;
-    const float a = (mA >= 0 && mA < L) ? ir_sample(xb, mA) : 0.0f;
-    const float c = (mB >= 0 && mB < L) ? ir_sample(xb, mB) : 0.0f;
+    const float a = (mA >= 0 && mA < L) ? air_pcm_sample(xb, mA) : 0.0f;
+    const float c = (mB >= 0 && mB < L) ? air_pcm_sample(xb, mB) : 0.0f;
     v[j] = cf{a, c};
     if (j >= PB_P / 256) xpeak = fmaxf(xpeak, fmaxf(fabsf(a), fabsf(c)));  // (even packing) blocks 2 m and 2 m + 1: every sample once
   }
@@ -685,7 +674,7 @@ __global__ __launch_bounds__(FC_NT) void pb_convolve_kernel(const T* __restrict_
                                                             unsigned* __restrict__ peaks, int n_ir, int nparts, int nz, int npair) {
   __shared__ cf buf[FC_LDS];
   const int b = blockIdx.y, t = threadIdx.x, j = blockIdx.x;
-  const int L = ir_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   float* __restrict__ yb = y + (size_t)b * Lcap;
   const int ir = idx ? min(idx[b], n_ir - 1) : 0;

@@ -4,7 +4,7 @@
 // dataset.py:69 without the host touching a sample.
 //
 // Random words: word(i, s) = word 0 of the Philox4x32-10 block at counter {i, s, 0, 0}, key {seed lo, seed hi} - the
-// generator of adv_head.hip / tests/philox_oracle.py.  s = (generation << 2) | kind: kind 0 / 1 the permutation of the
+// generator of air_philox.h / tests/philox_oracle.py.  s = (generation << 2) | kind: kind 0 / 1 the permutation of the
 // first / second flow, kind 2 the crop offsets.
 //
 // Permutation of n: key_i = word(i, s) << 32 | i, padded with all-ones sentinels in the layout air_eval_sort_keys
@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "air_common.h"
+#include "air_philox.h"
 
 namespace {
 
@@ -27,20 +28,8 @@ constexpr int CP_TILE_BYTES = 8192;  // per workgroup: two 16-byte chunks per la
 constexpr int CP_KIND_CROP = 2;
 
 __device__ __forceinline__ uint32_t cp_word(uint32_t i, uint32_t s, uint64_t seed) {
-  uint32_t c[4] = {i, s, 0u, 0u};
-  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0];
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k[0] += 0x9E3779B9u;
-    k[1] += 0xBB67AE85u;
-  }
+  uint32_t c[4];
+  air_philox_block((uint64_t)s << 32 | i, seed, c);
   return c[0];
 }
 

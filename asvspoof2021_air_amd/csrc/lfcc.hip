@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "air_common.h"
+#include "air_pcm.h"
 #include "air_prof.h"
 #include "air_fft16.h"
 
@@ -141,7 +142,7 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
   const float* __restrict__ row = a.pcm + (size_t)b * a.L;
   const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * a.L : nullptr;
   // sample m of this utterance as the float the reference's loader hands to LFCC.forward
-  auto sample = [&](long m) -> float { return row16 ? (float)row16[m] * (1.0f / 32768.0f) : row[m]; };
+  auto sample = [&](long m) -> float { return row16 ? air_pcm_sample(row16, m) : row[m]; };
 
   // ---- stage tables and pre-emphasised PCM ---------------------------------
   for (int e = tid; e < MAXW * MAXF; e += NTHREADS) s_fbwT[e] = plan->fbwT[e];

@@ -3,6 +3,7 @@
 // ecapa_tdnn.py:148-149).  Tiny tensors ((B,256,94), (B,512)): one workgroup per
 // utterance, everything staged in LDS, no intermediate ever reaches HBM.
 #include "air_common.h"
+#include "air_philox.h"
 
 namespace {
 
@@ -415,39 +416,14 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__
 // Philox4x32-10 counter-based generator -> N(0,1) via Box-Muller, scaled.
 // Replaces the host-side ``1e-5*torch.randn`` of resnet.py:38 (drawn on the CPU
 // and copied every call in the reference) with an on-device draw.
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0];
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-  k[0] += 0x9E3779B9u;
-  k[1] += 0xBB67AE85u;
-}
-
 __device__ __forceinline__ void randn_body(float* __restrict__ out, size_t n, uint64_t seed, uint64_t offset,
                                            float scale) {
   const size_t quad = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // 4 outputs each
   if (quad * 4 >= n) return;
-  const uint64_t ctr = offset + quad;
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-  uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) philox_round(c, k);
-  const float inv = 2.3283064365386963e-10f;  // 2^-32
+  uint32_t c[4];
+  air_philox_block(offset + quad, seed, c);
   float z[4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u1 = ((float)c[2 * h] + 1.0f) * inv;  // (0, 1]
-    const float u2 = (float)c[2 * h + 1] * inv;
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * h] = r * cs;
-    z[2 * h + 1] = r * sn;
-  }
+  air_philox_randn_quad(c, z);
   for (int j = 0; j < 4; ++j)
     if (quad * 4 + j < n) out[quad * 4 + j] = scale * z[j];
 }

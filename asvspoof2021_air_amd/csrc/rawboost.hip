@@ -29,6 +29,8 @@
 // Measured at B = 64 x 64 000 (profiles/rawboost.md): the LnL launch runs at the rate of the unpacked fp32 FMA, which is
 // what fir_kernel reached; the design launch is bound by the latency of its serial fp64 loops, not by arithmetic.
 #include "air_common.h"
+#include "air_pcm.h"
+#include "air_philox.h"
 
 namespace {
 
@@ -44,13 +46,6 @@ constexpr int RB_NSTAT = 6;                                // statistic slots pe
 constexpr int RB_MAXL = 1 << 20;                           // samples per row: what the host reserves per row in the ISD stream
 enum { RB_S_SUM = 0, RB_S_CMAX = 1, RB_S_QSQ = 2, RB_S_P3 = 3, RB_S_P4 = 4 };
 static_assert(RB_ROW == 164 && RB_GROUPS == 320, "the layout include/air_hip.h documents");
-
-__device__ __forceinline__ float rb_sample(const float* __restrict__ p, int i) { return p[i]; }
-__device__ __forceinline__ float rb_sample(const short* __restrict__ p, int i) { return (float)p[i] * (1.0f / 32768.0f); }  // exact
-
-__device__ __forceinline__ int rb_row_len(const int* __restrict__ lengths, int b, int Lcap) {
-  return lengths ? min(max(lengths[b], 1), Lcap) : Lcap;
-}
 
 // the table is caller data: anything that is not one of the eight algorithms copies the row
 __device__ __forceinline__ int rb_algo(const double* __restrict__ row) {
@@ -101,49 +96,20 @@ __device__ __forceinline__ double rb_merge_max(const double* __restrict__ stats,
   return s;
 }
 
-// ---- Philox4x32-10, as csrc/pool_head.hip and tests/philox_oracle.py state it ------------------------------------------
-__device__ __forceinline__ void rb_philox(uint64_t ctr, uint64_t key, uint32_t (&c)[4]) {
-  c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = 0u; c[3] = 0u;
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// four standard normals of one quad: the statements of air_randn's randn_body at scale 1
+// four standard normals of one quad of the air_randn stream (air_philox.h), at scale 1
 __device__ __forceinline__ void rb_randn_quad(uint64_t ctr, uint64_t key, float (&z)[4]) {
   uint32_t c[4];
-  rb_philox(ctr, key, c);
-  const float inv = 2.3283064365386963e-10f;  // 2^-32
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u1 = ((float)c[2 * h] + 1.0f) * inv;  // (0, 1]
-    const float u2 = (float)c[2 * h + 1] * inv;
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * h] = r * cs;
-    z[2 * h + 1] = r * sn;
-  }
+  air_philox_block(ctr, key, c);
+  air_philox_randn_quad(c, z);
 }
 
 // ISD, sample n of row b: selected iff word 0 < T; then v + g v (2 u1 - 1)(2 u2 - 1), every operation one fp32 rounding
 __device__ __forceinline__ float rb_isd(float v, uint64_t ctr, uint64_t key, uint64_t T, float g) {
   uint32_t c[4];
-  rb_philox(ctr, key, c);
+  air_philox_block(ctr, key, c);
   if ((uint64_t)c[0] >= T) return v;
-  const float inv = 2.3283064365386963e-10f;
-  const float a = 2.0f * ((float)c[1] * inv) - 1.0f;
-  const float d = 2.0f * ((float)c[2] * inv) - 1.0f;
+  const float a = 2.0f * air_philox_u01(c[1]) - 1.0f;
+  const float d = 2.0f * air_philox_u01(c[2]) - 1.0f;
   return v + (g * v) * (a * d);
 }
 
@@ -313,14 +279,14 @@ __global__ __launch_bounds__(RB_NT) void rb_lnl_kernel(const T* __restrict__ x, 
   __shared__ __attribute__((aligned(16))) float hs[RB_NF * RB_MAXTAPS];
   __shared__ double red[4];
   const int b = blockIdx.y, n0 = blockIdx.x * RB_T, t = threadIdx.x;
-  const int L = rb_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   if (!rb_has_lnl(rb_algo(params + (size_t)b * RB_ROW)) || n0 >= L) return;
   const T* __restrict__ xb = x + (size_t)b * Lcap;
   int jb_lo, jb_hi;
   rb_stage_taps<RB_NF>(taps, lens, b, 0, hs, t, jb_lo, jb_hi);
   for (int p = t; p < RB_GROUPS * 8; p += RB_NT) {
     const int m = n0 - (RB_MAXTAPS / 2 - 1) + p;
-    xs[(p >> 3) * RB_GS + (p & 7)] = (m >= 0 && m < L) ? rb_sample(xb, m) : 0.0f;
+    xs[(p >> 3) * RB_GS + (p & 7)] = (m >= 0 && m < L) ? air_pcm_sample(xb, m) : 0.0f;
   }
   __syncthreads();
   float out[RB_R];
@@ -348,7 +314,7 @@ __global__ __launch_bounds__(RB_NT) void rb_ssi_kernel(int Lcap, const int* __re
   __shared__ __attribute__((aligned(16))) float hs[RB_MAXTAPS];
   __shared__ double red[4];
   const int b = blockIdx.y, n0 = blockIdx.x * RB_T, t = threadIdx.x;
-  const int L = rb_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const double* __restrict__ row = params + (size_t)b * RB_ROW;
   if (!rb_has_ssi(rb_algo(row)) || n0 >= L) return;
   int jb_lo, jb_hi;
@@ -388,7 +354,7 @@ __global__ __launch_bounds__(RB_NT) void rb_centre_kernel(int Lcap, const int* _
                                                           float* __restrict__ A, double* __restrict__ stats, int ntcap) {
   __shared__ double red[4];
   const int b = blockIdx.y, n0 = blockIdx.x * RB_T, t = threadIdx.x;
-  const int L = rb_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   if (!rb_has_lnl(rb_algo(params + (size_t)b * RB_ROW)) || n0 >= L) return;
   const float mu = (float)(rb_merge_sum(stats, b, RB_S_SUM, ntcap, L) / (double)L);
   float* __restrict__ ab = A + (size_t)b * Lcap;
@@ -423,7 +389,7 @@ __global__ __launch_bounds__(RB_NT) void rb_point_kernel(int pass, const T* __re
                                                          double* __restrict__ stats, int ntcap) {
   __shared__ double red[4];
   const int b = blockIdx.y, n0 = blockIdx.x * RB_T, t = threadIdx.x;
-  const int L = rb_row_len(lengths, b, Lcap);
+  const int L = air_row_len(lengths, b, Lcap);
   const double* __restrict__ row = params + (size_t)b * RB_ROW;
   const int a = rb_algo(row);
   const T* __restrict__ xb = x + (size_t)b * Lcap;
@@ -435,7 +401,7 @@ __global__ __launch_bounds__(RB_NT) void rb_point_kernel(int pass, const T* __re
   if (pass == 0) {
     for (int n = max(n0, L) + t; n < min(n0 + RB_T, Lcap); n += RB_NT) yb[n] = 0.0f;  // (max(n0, L) + t: the tail only)
     if (a < 0) {
-      for (int n = n0 + t; n < nend; n += RB_NT) yb[n] = rb_sample(xb, n);
+      for (int n = n0 + t; n < nend; n += RB_NT) yb[n] = air_pcm_sample(xb, n);
       return;
     }
   }
@@ -450,7 +416,7 @@ __global__ __launch_bounds__(RB_NT) void rb_point_kernel(int pass, const T* __re
       for (int n = n0 + t; n < nend; n += RB_NT) yb[n] = rb_n0(ab[n], pk);
     } else if (a == 5 || a == 2) {
       for (int n = n0 + t; n < nend; n += RB_NT) {
-        const float v = a == 5 ? rb_n0(ab[n], pk) : rb_sample(xb, n);
+        const float v = a == 5 ? rb_n0(ab[n], pk) : air_pcm_sample(xb, n);
         wb[n] = v;
         stat += (double)v * (double)v;
       }
@@ -462,7 +428,7 @@ __global__ __launch_bounds__(RB_NT) void rb_point_kernel(int pass, const T* __re
       const bool chained = a == 3 || a == 4;
       float peak = 0.0f;
       for (int n = n0 + t; n < nend; n += RB_NT) {
-        const float v = chained ? rb_n0(ab[n], pk) : rb_sample(xb, n);
+        const float v = chained ? rb_n0(ab[n], pk) : air_pcm_sample(xb, n);
         const float w = rb_isd(v, base + (uint64_t)n, key, T64, g);
         wb[n] = w;
         peak = fmaxf(peak, fabsf(w));

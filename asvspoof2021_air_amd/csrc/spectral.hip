@@ -24,6 +24,7 @@
 
 #include "air_common.h"
 #include "air_fft16.h"
+#include "air_pcm.h"
 
 namespace {
 
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void spec_kernel(SpecArgs a) {
   }
   const float* __restrict__ row = a.pcm ? a.pcm + (size_t)b * a.L : nullptr;
   const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * a.L : nullptr;
-  auto sample = [&](long m) -> float { return row16 ? (float)row16[m] * (1.0f / 32768.0f) : row[m]; };
+  auto sample = [&](long m) -> float { return row16 ? air_pcm_sample(row16, m) : row[m]; };
 
   // ---- stage the filter weights and the PCM --------------------------------
   if constexpr (MEL) {

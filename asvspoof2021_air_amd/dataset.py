@@ -30,7 +30,7 @@ import torch
 from torch.utils.data import Dataset
 from torch.utils.data.dataloader import default_collate
 
-from . import _hip
+from . import _hip, ragged
 from .feature_extraction import LFCC, STFT, Melspec, pad_mode_id
 
 
@@ -368,28 +368,12 @@ class _SpoofDataset(Dataset):
     PINNED_RING = 6
 
     def _pinned_batch(self, B, L, dtype):
-        """A pinned (B, L) host buffer out of a ring of PINNED_RING per shape: allocating pinned memory per batch cost
-        ~20 ms of host time per 16 MB batch on the GPU box (the from-dataset bench leg was host-bound at 0.48 of the
-        resident rate).  A batch stays valid until PINNED_RING - 1 further batches have been collated; before a slot is
-        reused, the H2D copy ``DevicePrefetcher`` issued from it is waited for (normally long done)."""
-        if not torch.cuda.is_available():
-            return torch.empty((B, L), dtype=dtype)
-        ring = self.__dict__.setdefault("_pin_ring", {})
-        key = (B, L, dtype)
-        slot = ring.get(key)
-        if slot is None:
-            slot = ring[key] = {"bufs": [None] * self.PINNED_RING, "events": [None] * self.PINNED_RING, "next": 0}
-        j = slot["next"]
-        slot["next"] = (j + 1) % self.PINNED_RING
-        if slot["bufs"][j] is None:
-            slot["bufs"][j] = torch.empty((B, L), dtype=dtype, pin_memory=True)
-        ev = slot["events"][j]
-        if ev is not None:
-            ev.synchronize()
-            slot["events"][j] = None
-        buf = slot["bufs"][j]
-        buf._air_ring = (slot["events"], j)  # (the events list, not the slot: the slot holds the buffer - no reference cycle)
-        return buf
+        """A pinned (B, L) host buffer out of this dataset's ring of PINNED_RING per shape (``ragged.PinnedRing``): a batch
+        stays valid until PINNED_RING - 1 further batches have been collated."""
+        ring = self.__dict__.get("_pin_ring")
+        if ring is None:
+            ring = self._pin_ring = ragged.PinnedRing(self.PINNED_RING)
+        return ring.take((B, L, dtype), (B, L), dtype)
 
     def collate_fn(self, samples):
         """default_collate of the item tuples (dataset.py:87-89).  With ``return_pcm`` the waveforms become features
@@ -451,7 +435,7 @@ class _SpoofDataset(Dataset):
         return [out.unsqueeze(1).transpose(2, 3)] + list(rest)
 
 
-    RAGGED_ROUND = 16000  # ragged_samples None: the capacity is the longest utterance rounded up to this
+    RAGGED_ROUND = ragged.RAGGED_ROUND  # ragged_samples None: the capacity is the longest utterance rounded up to this
 
     def _collate_ragged(self, samples):
         """``return_pcm='ragged'``: utterances of ANY length as one pinned (B, Lcap) host tensor (tails zero-filled) + int32
@@ -466,7 +450,7 @@ class _SpoofDataset(Dataset):
         lens = [int(smp[0].shape[0]) for smp in samples]
         cap = self.ragged_samples
         if cap is None:
-            cap = -(-max(lens) // self.RAGGED_ROUND) * self.RAGGED_ROUND
+            cap = ragged.round_capacity(max(lens))
         else:
             cap = int(cap)
             for smp, n in zip(samples, lens):

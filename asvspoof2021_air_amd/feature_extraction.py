@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from .ragged import device_lengths, pcm_pointers
 
 
 def trimf(x, params):
@@ -77,6 +78,13 @@ def pad_mode_id(padding):
     return PAD_MODES[padding]
 
 
+def _pcm_source(x):
+    """What the kernels read ``x`` as: int16 PCM or float32, contiguous; any other dtype is converted with ``.float()``."""
+    if x.dtype in (torch.int16, torch.float32):
+        return x.contiguous()
+    return x.float().contiguous()
+
+
 class LFCC(nn.Module):
     """LFCC(fl, fs, fn, sr, filter_num, with_energy=False, with_emphasis=True, with_delta=True)."""
 
@@ -139,7 +147,7 @@ class LFCC(nn.Module):
         if x.dtype == torch.int16:  # raw 16-bit PCM: nothing to mutate (the reference never sees integers)
             return self._forward_i16(x, 0, None)
         T = 1 + L // self.fs
-        src = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
+        src = _pcm_source(x)
         out = torch.empty((B, T, self.out_dim), device=x.device, dtype=torch.float32)
         lib = _hip.lib()
         _hip.check(lib.air_lfcc_fwd(_hip.dptr(src), _hip.ci(B), _hip.ci(L), _hip.dptr(out),
@@ -173,14 +181,11 @@ class LFCC(nn.Module):
         self._check(x)
         mode = pad_mode_id(padding)
         B, L = x.shape
-        i16 = x.dtype == torch.int16
-        src = x.contiguous() if i16 else (x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous())
+        src = _pcm_source(x)
         out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
         sil = self.silence_row(x.device) if mode == 2 else None
         lib = _hip.lib()
-        null = _hip.dptr(None, allow_none=True)
-        _hip.check(lib.air_lfcc_fwd_padded_ex(null if i16 else _hip.dptr(src),
-                                              _hip.dptr(src, torch.int16) if i16 else null,
+        _hip.check(lib.air_lfcc_fwd_padded_ex(*pcm_pointers(src),
                                               _hip.ci(B), _hip.ci(L), _hip.dptr(out),
                                               _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
                                               _hip.dptr(self.plan(x.device), torch.uint8),
@@ -198,27 +203,14 @@ class LFCC(nn.Module):
         self._check(x)
         mode = pad_mode_id(padding)
         B, Lcap = x.shape
-        if not (torch.is_tensor(lengths) and lengths.is_cuda):
-            host = torch.as_tensor(lengths).reshape(-1)
-            if host.numel() != B or host.is_floating_point():
-                raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
-            if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
-                raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
-                    Lcap, int(host.min()), int(host.max())))
-            lengths = host.to(torch.int32).to(x.device)
-        elif lengths.numel() != B:
-            raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
-        lengths = lengths.to(torch.int32).contiguous()  # (no-op for what the dataset hands over)
+        lengths = device_lengths(lengths, B, Lcap, x.device)
         if start is not None and not (torch.is_tensor(start) and start.is_cuda):
             start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
-        i16 = x.dtype == torch.int16
-        src = x.contiguous() if i16 else (x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous())
+        src = _pcm_source(x)
         out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
         sil = self.silence_row(x.device) if mode == 2 else None
         lib = _hip.lib()
-        null = _hip.dptr(None, allow_none=True)
-        _hip.check(lib.air_lfcc_fwd_ragged(null if i16 else _hip.dptr(src),
-                                           _hip.dptr(src, torch.int16) if i16 else null,
+        _hip.check(lib.air_lfcc_fwd_ragged(*pcm_pointers(src),
                                            _hip.ci(B), _hip.ci(Lcap), _hip.dptr(lengths, torch.int32), _hip.dptr(out),
                                            _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
                                            _hip.dptr(self.plan(x.device), torch.uint8),
@@ -292,24 +284,16 @@ class _Spectral(nn.Module):
             raise _hip.AirError("%s HIP path needs a GPU tensor; there is no CPU fallback" % self.NAME)
 
     def _check_lengths(self, host, Lcap):
-        """Host-side lengths beyond the [1, Lcap] check that ``forward_ragged`` shares with LFCC."""
-
-    @staticmethod
-    def _src(x):
-        if x.dtype == torch.int16:
-            return x.contiguous(), True
-        return (x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()), False
+        """Host-side lengths beyond the [1, Lcap] check of ``ragged.device_lengths``."""
 
     def _dense(self, x):
         """(B, L) float32 or int16 on the GPU -> (B, T, out_dim).  Does not mutate ``x``."""
         self._check(x)
         B, L = x.shape
         self._check_lengths(torch.tensor([L]), L)
-        src, i16 = self._src(x)
+        src = _pcm_source(x)
         out = torch.empty((B, 1 + L // self.fs, self.out_dim), device=x.device, dtype=torch.float32)
-        null = _hip.dptr(None, allow_none=True)
-        _hip.check(_hip.lib().air_spec_fwd(_hip.ci(self.KIND), null if i16 else _hip.dptr(src),
-                                           _hip.dptr(src, torch.int16) if i16 else null, _hip.ci(B), _hip.ci(L),
+        _hip.check(_hip.lib().air_spec_fwd(_hip.ci(self.KIND), *pcm_pointers(src), _hip.ci(B), _hip.ci(L),
                                            _hip.dptr(out), _hip.dptr(self.plan(x.device), torch.uint8),
                                            _hip.ci(self._flags()), _hip.stream()), "air_spec_fwd")
         return out, src
@@ -319,11 +303,9 @@ class _Spectral(nn.Module):
         B, Lcap = x.shape
         if start is not None and not (torch.is_tensor(start) and start.is_cuda):
             start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
-        src, i16 = self._src(x)
+        src = _pcm_source(x)
         out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
-        null = _hip.dptr(None, allow_none=True)
-        _hip.check(_hip.lib().air_spec_fwd_ragged(_hip.ci(self.KIND), null if i16 else _hip.dptr(src),
-                                                  _hip.dptr(src, torch.int16) if i16 else null, _hip.ci(B), _hip.ci(Lcap),
+        _hip.check(_hip.lib().air_spec_fwd_ragged(_hip.ci(self.KIND), *pcm_pointers(src), _hip.ci(B), _hip.ci(Lcap),
                                                   _hip.dptr(lengths, torch.int32, True), _hip.dptr(out), _hip.ci(feat_len),
                                                   _hip.dptr(start, torch.int32, True),
                                                   _hip.dptr(self.plan(x.device), torch.uint8), _hip.ci(self._flags()),
@@ -345,18 +327,8 @@ class _Spectral(nn.Module):
         is checked (ValueError) and uploaded."""
         self._check(x, padding)
         B, Lcap = x.shape
-        if not (torch.is_tensor(lengths) and lengths.is_cuda):
-            host = torch.as_tensor(lengths).reshape(-1)
-            if host.numel() != B or host.is_floating_point():
-                raise ValueError("lengths must be %d integers, got %s %s" % (B, tuple(host.shape), host.dtype))
-            if B and (int(host.min()) < 1 or int(host.max()) > Lcap):
-                raise ValueError("lengths must lie in [1, %d] (the row capacity), got [%d, %d]" % (
-                    Lcap, int(host.min()), int(host.max())))
-            self._check_lengths(host, Lcap)
-            lengths = host.to(torch.int32).to(x.device)
-        elif lengths.numel() != B:
-            raise ValueError("lengths must have %d entries, got %d" % (B, lengths.numel()))
-        return self._padded(x, lengths.to(torch.int32).contiguous(), feat_len, start, padding)
+        lengths = device_lengths(lengths, B, Lcap, x.device, extra_check=self._check_lengths)
+        return self._padded(x, lengths, feat_len, start, padding)
 
 
 class STFT(_Spectral):

@@ -10,13 +10,13 @@ Served: 16-bit mono streams of one block size (what the ASVspoof 2019 / 2021 cor
 everything else on the host, by name; the device reports per row what it could not decode (``STATUS``), never faults.
 """
 import collections
-import ctypes
 import hashlib
 
 import numpy as np
 import torch
 
 from . import _hip
+from .ragged import RAGGED_ROUND, DeviceRing, PinnedRing, check_status, round_capacity  # noqa: F401  (RAGGED_ROUND: re-exported)
 
 FlacInfo = collections.namedtuple("FlacInfo", "min_blocksize max_blocksize min_framesize max_framesize sample_rate "
                                   "channels bits_per_sample total_samples md5 audio_offset")
@@ -25,7 +25,6 @@ FlacInfo = collections.namedtuple("FlacInfo", "min_blocksize max_blocksize min_f
 OK, LOST_SYNC, BAD_CRC16, UNSUPPORTED, LENGTH_MISMATCH, CANDIDATE_OVERFLOW = range(6)
 STATUS = {OK: "OK", LOST_SYNC: "LOST_SYNC", BAD_CRC16: "BAD_CRC16", UNSUPPORTED: "UNSUPPORTED",
           LENGTH_MISMATCH: "LENGTH_MISMATCH", CANDIDATE_OVERFLOW: "CANDIDATE_OVERFLOW"}
-RAGGED_ROUND = 16000  # dataset._SpoofDataset.RAGGED_ROUND: the default row capacity is the longest row rounded up to this
 
 
 class FlacError(RuntimeError):
@@ -101,29 +100,12 @@ class FlacSource:
 
 
 PINNED_RING = 6
-_pin_ring = {}
+_pin_ring = PinnedRing(PINNED_RING)
 
 
 def _pinned_bytes(cap):
-    """A pinned uint8 buffer out of a ring of PINNED_RING per capacity (dataset._SpoofDataset._pinned_batch: allocating
-    pinned memory per batch is host time per batch).  DevicePrefetcher stores the event of its copy in ``_air_ring``;
-    a slot is reused only behind it."""
-    if not torch.cuda.is_available():
-        return torch.empty(cap, dtype=torch.uint8)
-    slot = _pin_ring.get(cap)
-    if slot is None:
-        slot = _pin_ring[cap] = {"bufs": [None] * PINNED_RING, "events": [None] * PINNED_RING, "next": 0}
-    j = slot["next"]
-    slot["next"] = (j + 1) % PINNED_RING
-    if slot["bufs"][j] is None:
-        slot["bufs"][j] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-    ev = slot["events"][j]
-    if ev is not None:
-        ev.synchronize()
-        slot["events"][j] = None
-    buf = slot["bufs"][j]
-    buf._air_ring = (slot["events"], j)
-    return buf
+    """A pinned uint8 buffer out of the module's ring, per capacity."""
+    return _pin_ring.take(cap, cap, torch.uint8)
 
 
 def pack_rows(rows, bytes_round=65536):
@@ -159,25 +141,12 @@ def pack(items, bytes_round=65536):
     return buf, off, lengths, blocksize
 
 
-class FlacDecoder:
-    """The device decoder.  Output, status and workspace tensors come out of a ring of ``depth`` slots per shape, as
-    DevicePrefetcher's do: a replayed step sees stable addresses, and a result stays valid until ``depth - 1`` further
-    calls of the same shape."""
+class FlacDecoder(DeviceRing):
+    """The device decoder.  Output, status and workspace tensors come out of a ring of ``depth`` slots per shape
+    (``ragged.DeviceRing``)."""
 
     def __init__(self, device="cuda", depth=4):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _hip.AirError("FlacDecoder runs on the GPU (the HIP path has no CPU fallback)")
-        self.depth = max(1, int(depth))
-        self._ring, self._next = {}, {}
-
-    def _slot(self, key, make):
-        ring = self._ring.setdefault(key, [])
-        j = self._next.get(key, 0)
-        self._next[key] = (j + 1) % self.depth
-        if j >= len(ring):
-            ring.append(make())
-        return ring[j]
+        super().__init__(device, depth)
 
     def decode(self, bytes_dev, byte_off, lengths, blocksize, Lcap=None, dtype=torch.int16, check=False, out=None):
         """-> (pcm (B, Lcap) int16 | float32 = sample / 32768, status (B,) int32), both on the device.  Tails beyond
@@ -185,34 +154,23 @@ class FlacDecoder:
         ``ragged_samples``); ``Lcap=None`` takes the longest length rounded up to RAGGED_ROUND, which reads ``lengths``
         (a copy if they live on the device).  ``check=True`` calls ``check(status)`` (synchronous).  ``out``: a
         contiguous (B, Lcap) device tensor of ``dtype`` to decode into instead of the ring's."""
-        if dtype not in (torch.int16, torch.float32):
-            raise ValueError("dtype is torch.int16 or torch.float32")
         L = _hip.lib()
         B = int(lengths.shape[0])
         if byte_off.shape[0] != B + 1 or blocksize.shape[0] != B:
             raise ValueError("byte_off has B + 1 entries, lengths and blocksize B")
         if Lcap is None:
-            Lcap = -(-max(1, int(lengths.max())) // RAGGED_ROUND) * RAGGED_ROUND
+            Lcap = round_capacity(lengths.max())
         Lcap = int(Lcap)
         dev = self.device
         byte_off, lengths, blocksize = (t.to(dev, non_blocking=True) for t in (byte_off, lengths, blocksize))
         total = int(bytes_dev.numel())
         ws_bytes = L.air_flac_workspace_bytes(_hip.csz(total), _hip.ci(B))
-        if out is not None:
-            if tuple(out.shape) != (B, Lcap) or out.dtype != dtype:
-                raise ValueError("out must be a (%d, %d) %s tensor" % (B, Lcap, dtype))
-            pcm = out
-        else:
-            pcm = self._slot(("pcm", B, Lcap, dtype), lambda: torch.empty((B, Lcap), dtype=dtype, device=dev))
-        status = self._slot(("status", B), lambda: torch.empty(B, dtype=torch.int32, device=dev))
+        pcm, status, p16, p32 = self._output(B, Lcap, dtype, out)
         ws = self._slot(("ws", ws_bytes), lambda: torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev))
-        null = ctypes.c_void_p(0)
         _hip.check(L.air_flac_decode(_hip.dptr(bytes_dev, torch.uint8), _hip.csz(total), _hip.dptr(byte_off, torch.int32),
                                      _hip.dptr(lengths, torch.int32), _hip.dptr(blocksize, torch.int32), _hip.ci(B),
-                                     _hip.ci(Lcap), _hip.dptr(pcm, torch.int16) if dtype == torch.int16 else null,
-                                     _hip.dptr(pcm, torch.float32) if dtype == torch.float32 else null,
-                                     _hip.dptr(status, torch.int32), _hip.dptr(ws, torch.uint8), _hip.csz(ws_bytes),
-                                     _hip.stream()), "air_flac_decode")
+                                     _hip.ci(Lcap), p16, p32, _hip.dptr(status, torch.int32), _hip.dptr(ws, torch.uint8),
+                                     _hip.csz(ws_bytes), _hip.stream()), "air_flac_decode")
         if check:
             self.check(status)
         return pcm, status
@@ -221,10 +179,7 @@ class FlacDecoder:
     def check(status):
         """Copy ``status`` to the host (synchronises) and raise FlacError listing the rows that are not OK.  Once per
         epoch over the concatenated statuses is enough."""
-        st = status.detach().cpu().reshape(-1).tolist()
-        bad = [(r, c) for r, c in enumerate(st) if c != OK]
-        if bad:
-            raise FlacError(bad)
+        check_status(status, OK, FlacError)
 
 
 def check(status):

@@ -17,10 +17,10 @@ import numpy as np
 import torch
 
 from . import _hip
+from .ragged import RAGGED_ROUND, DeviceRing, check_status, round_capacity  # noqa: F401  (RAGGED_ROUND, DeviceRing: re-exported)
 
 TARGET_SR = 16000
 MAX_RATES = 8           # AIR_RESAMPLE_MAX_RATES: distinct source rates of one batch
-RAGGED_ROUND = 16000    # the default row capacity is the longest output row rounded up to this
 # sample kinds of include/air_hip.h (AIR_PCM_*) and their bytes per sample
 U8, S16, S24, S32, F32, F64 = range(6)
 KIND_BYTES = {U8: 1, S16: 2, S24: 3, S32: 4, F32: 4, F64: 8}
@@ -91,26 +91,6 @@ def distinct(rates):
     return seen
 
 
-class DeviceRing:
-    """Output, status and index tensors out of a ring of ``depth`` slots per key, as flac.FlacDecoder's: a replayed step
-    sees stable addresses, and a result stays valid until ``depth - 1`` further calls of the same shape."""
-
-    def __init__(self, device, depth):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _hip.AirError("%s runs on the GPU (the HIP path has no CPU fallback)" % type(self).__name__)
-        self.depth = max(1, int(depth))
-        self._ring, self._next = {}, {}
-
-    def _slot(self, key, make):
-        ring = self._ring.setdefault(key, [])
-        j = self._next.get(key, 0)
-        self._next[key] = (j + 1) % self.depth
-        if j >= len(ring):
-            ring.append(make())
-        return ring[j]
-
-
 class RateBank(DeviceRing):
     """The per-rate coefficient tables on the device and the per-batch records.  A table is computed once per rate
     (host, fp64 -> fp32) and appended to one device buffer; a batch's record list, its per-row index and per-row L / M
@@ -169,20 +149,6 @@ class RateBank(DeviceRing):
         """ceil(n L / M) per row on the host (``n``: B ints)."""
         return [out_length(int(v), sr, self.target_sr) for v, sr in zip(n, rates)]
 
-    def _output(self, B, Lcap, dtype, out):
-        if dtype not in (torch.int16, torch.float32):
-            raise ValueError("dtype is torch.int16 or torch.float32")
-        if out is not None:
-            if tuple(out.shape) != (B, Lcap) or out.dtype != dtype or not out.is_contiguous():
-                raise ValueError("out must be a contiguous (%d, %d) %s tensor" % (B, Lcap, dtype))
-            pcm = out
-        else:
-            pcm = self._slot(("pcm", B, Lcap, dtype), lambda: torch.empty((B, Lcap), dtype=dtype, device=self.device))
-        status = self._slot(("status", B), lambda: torch.empty(B, dtype=torch.int32, device=self.device))
-        null = ctypes.c_void_p(0)
-        return (pcm, status, _hip.dptr(pcm, torch.int16) if dtype == torch.int16 else null,
-                _hip.dptr(pcm, torch.float32) if dtype == torch.float32 else null)
-
 
 class ResampleError(RuntimeError):
     """Rows of a batch the device refused: ``rows`` = [(row, status code), ...]."""
@@ -195,10 +161,7 @@ class ResampleError(RuntimeError):
 
 def check(status, what="resample"):
     """Copy ``status`` to the host (synchronises) and raise ResampleError listing the rows that are not OK."""
-    st = status.detach().cpu().reshape(-1).tolist()
-    bad = [(r, c) for r, c in enumerate(st) if c != OK]
-    if bad:
-        raise ResampleError(bad, what)
+    check_status(status, OK, lambda rows: ResampleError(rows, what))
 
 
 _check = check
@@ -224,7 +187,7 @@ class Resampler(RateBank):
         rates = rate_list(rates, B)
         desc, idx, Lrow, Mrow, tables, used = self.plan(rates)
         if Lcap is None:
-            Lcap = -(-max(1, max(self.host_lengths(lengths.detach().cpu().tolist(), rates))) // RAGGED_ROUND) * RAGGED_ROUND
+            Lcap = round_capacity(max(self.host_lengths(lengths.detach().cpu().tolist(), rates)))
         Lcap = int(Lcap)
         lengths = lengths.to(self.device, non_blocking=True)
         if lengths.dtype != torch.int32:

@@ -24,6 +24,7 @@ from .feature_extraction import LFCC
 from .hip_model import HipModel
 from .loss import AngularIsoLoss, IsolateLoss, IsolateSquareLoss, P2SGradLoss
 from .optim import FusedAdam, FusedSGD
+from .ragged import device_lengths
 
 
 def adjust_learning_rate(lr0, optimizer, epoch_num, lr_decay=0.5, interval=30):
@@ -618,15 +619,8 @@ class Trainer:
 
     def _ragged_lengths(self, lengths, pcm):
         """``lengths`` as the int32 (B,) device tensor a replay copies into the capture's buffer; host values are checked
-        like LFCC.forward_ragged checks them."""
-        if not (torch.is_tensor(lengths) and lengths.is_cuda):
-            host = torch.as_tensor(lengths).reshape(-1)
-            if host.numel() != pcm.shape[0] or host.is_floating_point() or int(host.min()) < 1 or int(host.max()) > pcm.shape[1]:
-                raise ValueError("lengths must be %d integers in [1, %d]" % (pcm.shape[0], pcm.shape[1]))
-            lengths = host.to(torch.int32).to(pcm.device, non_blocking=True)
-        if lengths.numel() != pcm.shape[0]:
-            raise ValueError("lengths must have %d entries, got %d" % (pcm.shape[0], lengths.numel()))
-        return lengths
+        (``ragged.device_lengths``)."""
+        return device_lengths(lengths, pcm.shape[0], pcm.shape[1], pcm.device, non_blocking=True)
 
     def _capture_or_fall_back(self, key, pcm, labels, lengths=None, start=None):
         """The capture, guarded for world > 1: were it to fail on ANY rank (a runtime that refuses a call inside a

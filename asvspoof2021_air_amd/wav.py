@@ -18,7 +18,7 @@ import struct
 import numpy as np
 import torch
 
-from . import _hip, flac, resample
+from . import _hip, flac, ragged, resample
 from .resample import BAD_FORMAT, F32, F64, KIND_BYTES, LENGTH_MISMATCH, OK, S16, S24, S32, STATUS, U8  # noqa: F401
 
 WavInfo = collections.namedtuple("WavInfo", "kind channels sample_rate bits block_align frames data_offset")
@@ -169,8 +169,7 @@ class WavDecoder(resample.RateBank):
         rate = resample.rate_list(rate, B)
         desc, idx, _, _, tables, used = self.plan(rate)
         if Lcap is None:
-            longest = max(self.host_lengths(frames.detach().cpu().tolist(), rate))
-            Lcap = -(-max(1, longest) // resample.RAGGED_ROUND) * resample.RAGGED_ROUND
+            Lcap = ragged.round_capacity(max(self.host_lengths(frames.detach().cpu().tolist(), rate)))
         Lcap = int(Lcap)
         dev = self.device
         byte_off, frames, fmt = (t.to(dev, non_blocking=True) for t in (byte_off, frames, fmt))
@@ -188,10 +187,7 @@ class WavDecoder(resample.RateBank):
     def check(status):
         """Copy ``status`` to the host (synchronises) and raise WavError listing the rows that are not OK.  Once per
         epoch over the concatenated statuses is enough."""
-        st = status.detach().cpu().reshape(-1).tolist()
-        bad = [(r, c) for r, c in enumerate(st) if c != OK]
-        if bad:
-            raise WavError(bad)
+        ragged.check_status(status, OK, WavError)
 
 
 def check(status):

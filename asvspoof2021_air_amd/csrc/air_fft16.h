@@ -1,5 +1,6 @@
-// 16-point complex FFT in registers on packed fp32 pairs (shared by the LFCC front-end, csrc/lfcc.hip, and the FFT form of the
-// impulse-response convolution, csrc/augment.hip).
+// 16-point complex FFT in registers on packed fp32 pairs.  Users: the 512-point spectrum pipeline of the PCM front-ends
+// (csrc/air_spec512.h, and through it csrc/lfcc.hip and csrc/spectral.hip, which also call fft16 for the first pass) and
+// the FFT form of the impulse-response convolution (csrc/augment.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

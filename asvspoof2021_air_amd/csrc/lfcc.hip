@@ -18,13 +18,18 @@
 // held by lane (16-q) of the same 16-lane group.  torch.stft centres the
 // 320-tap window inside the 512 frame (offset 96); placing it at offset 0
 // only changes the phase, which |X|^2 discards.
+//
+// Everything up to the power spectrum, the ragged row geometry and both
+// copy-outs are the pieces of air_spec512.h, shared with the STFT and Melspec
+// kernels of csrc/spectral.hip; the window multiply (held in registers across
+// the barrier), the filterbank, log, DCT and deltas are this file's own.  One
+// shared piece, the PCM staging loop, is stated here again (see lfcc_body).
 #include <math.h>
 #include <string.h>
 
 #include "air_common.h"
-#include "air_pcm.h"
 #include "air_prof.h"
-#include "air_fft16.h"
+#include "air_spec512.h"
 
 namespace {
 
@@ -50,7 +55,6 @@ constexpr int FCOMP = NW * GPW * 4;     // 32 frames computed per workgroup
 constexpr int HALO = 2;                 // delta-delta reaches 2 frames each side
 constexpr int FOUT = FCOMP - 2 * HALO;  // 28 frames written per workgroup
 constexpr int NSAMP = FS * (FCOMP + 1); // 5,280 staged samples
-constexpr int XROW = 17;                // padded transpose row (complex elements)
 // wave-private exchange tile: the 4 x 16 x 17 transposition (real and imaginary parts in two passes), then the 4
 // power rows + 4 x 32 filterbank outputs; 69.6 KB for the workgroup - two workgroups per CU (round 1: one)
 constexpr int XCH_FLOATS = 4 * 264 + 4 * 32;
@@ -68,15 +72,6 @@ struct LfccPlan {
   float dctT[MAXF * MAXF];    // [j][i] = dct[i][j]
 };
 
-__device__ __constant__ const float W32C[16] = {
-    1.000000000f, 0.980785280f, 0.923879533f, 0.831469612f, 0.707106781f, 0.555570233f,
-    0.382683432f, 0.195090322f, 0.000000000f, -0.195090322f, -0.382683432f, -0.555570233f,
-    -0.707106781f, -0.831469612f, -0.923879533f, -0.980785280f};
-__device__ __constant__ const float W32S[16] = {
-    0.000000000f, 0.195090322f, 0.382683432f, 0.555570233f, 0.707106781f, 0.831469612f,
-    0.923879533f, 0.980785280f, 1.000000000f, 0.980785280f, 0.923879533f, 0.831469612f,
-    0.707106781f, 0.555570233f, 0.382683432f, 0.195090322f};
-
 struct LfccArgs {
   const float* pcm;
   const short* pcm16;  // non-null: 16-bit PCM as stored in the corpus' wav/flac files; x = s / 32768 (exact)
@@ -91,18 +86,10 @@ struct LfccArgs {
 struct LfccRaggedArgs : LfccArgs {
   const int* lengths;  // (B,) samples of each row, clamped to [1, L] on the device
 };
-// (A/B knob: -DLFCC_RAGGED_NOSKIP=1 lets the dead tiles of a ragged row stage and compute like live ones - what the
-// early exit is worth, profiles/ragged_lfcc.md)
-#ifndef LFCC_RAGGED_NOSKIP
-#define LFCC_RAGGED_NOSKIP 0
-#endif
 
 constexpr int FLAG_EMPH = AIR_LFCC_EMPHASIS;
 constexpr int FLAG_DELTA = AIR_LFCC_DELTA;
 constexpr int FLAG_PADDED = 1 << 8;  // internal: (B, D, feat_len) output
-#ifndef LFCC_EXACT_NORM
-#define LFCC_EXACT_NORM 0
-#endif
 
 // NF_C / MW_C > 0: the filter count and the widest filter are compile-time (the reference's LFCC(320, 160, 512, 16000,
 // 20): 20 filters, 26 bins) - the filterbank and DCT loops unroll onto immediate LDS offsets with no index arithmetic
@@ -110,7 +97,7 @@ constexpr int FLAG_PADDED = 1 << 8;  // internal: (B, D, feat_len) output
 // profiles/r05_lfcc.md - and ~40 % of them were address arithmetic, clamps and the correctly rounded sqrt).  0: any plan.
 // RAGGED (Args = LfccRaggedArgs, padded layout only): the row's own L and T come from a.lengths[b]; a workgroup whose
 // tile holds no frame the row writes leaves before it stages anything.  Every tile computes its own halo, so the tiles
-// that stay write what they would have written.  The fixed-length instantiation compiles to the code it always had.
+// that stay write what they would have written.  The fixed-length instantiation holds no trace of it.
 template <int NF_C, int MW_C, bool RAGGED = false, class Args = LfccArgs>
 __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_pcm, float* __restrict__ s_xch,
                                           float* __restrict__ s_c, float* __restrict__ s_fbwT,
@@ -126,18 +113,12 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
   const int maxw = MW_C ? MW_C : plan->maxw;
   int L = a.L, T = a.T;
   int live_tiles = a.tiles;  // tiles of this row that write frames: they share the row's constant frames
-  bool dead = false;         // ragged: this tile holds no frame that the row writes
   if constexpr (RAGGED) {
-    L = min(max(a.lengths[b], 1), a.L);  // a bad length in device memory must not read outside the row
-    T = 1 + L / FS;
-    live_tiles = (T + FOUT - 1) / FOUT;
-    dead = t0 >= T;
-    if (T > a.feat_len) {
-      // chopped row: only the tiles that overlap [start, start + feat_len) are written (same clamp as below)
-      const int st = a.start != nullptr ? min(max(a.start[b], 0), T - a.feat_len) : 0;
-      dead = dead || t0 + FOUT <= st || t0 >= st + a.feat_len;
-    }
-    if (!LFCC_RAGGED_NOSKIP && dead) return;  // (workgroup-uniform, ahead of every barrier)
+    const Spec512Row r = spec512_row<FS, FOUT, false>(a.lengths, a.start, b, a.L, a.feat_len, t0);
+    if (r.dead) return;  // (workgroup-uniform, ahead of every barrier)
+    L = r.L;
+    T = r.T;
+    live_tiles = r.live_tiles;
   }
   const float* __restrict__ row = a.pcm + (size_t)b * a.L;
   const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * a.L : nullptr;
@@ -148,6 +129,10 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
   for (int e = tid; e < MAXW * MAXF; e += NTHREADS) s_fbwT[e] = plan->fbwT[e];
   for (int e = tid; e < MAXF * MAXF; e += NTHREADS) s_dctT[e] = plan->dctT[e];
   const long s0 = (long)FS * (t0 - HALO) - FL / 2;  // first staged sample (may be < 0)
+  // The staging loop is spec512_stage (air_spec512.h) without the reflect branch, and the one shared piece stated here
+  // again: behind the helper hipcc splits the float4 load of the emphasised path and re-derives the edge compares, and
+  // the launch measured 26.9 us for 26.7 (B = 64 x 4 s, profiles/spectral_frontends.md).  A change to either copy
+  // belongs in both; test_lfcc_is_filterbank_log_dct_of_the_stft_kernels_spectrum holds the two to one spectrum.
   const bool emph = (a.flags & FLAG_EMPH) != 0;
   const bool vec_ok = row16 == nullptr && ((((size_t)row) & 15) == 0);
   for (int e4 = tid; e4 < NSAMP / 4; e4 += NTHREADS) {
@@ -194,12 +179,10 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
     const int n = (g * q) & 255;
     tw[q] = cf{plan->tw256[2 * n], plan->tw256[2 * n + 1]};
   }
-  const float cq = plan->tw512[2 * g];        //  cos(2 pi g/512)
-  const float sq = -plan->tw512[2 * g + 1];   //  sin(2 pi g/512)
+  const Spec512Lane ln = spec512_lane(plan->tw512, lane);
   const int j0 = g, j1 = g + 16;
   const int lo0 = plan->lo[j0];
   const int lo1 = plan->lo[j1 < MAXF ? j1 : 0];
-  const int partner = (lane & 48) | ((16 - g) & 15);
   float* xch = s_xch + wave * XCH_FLOATS;
 
   __syncthreads();
@@ -224,62 +207,10 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
     fft16<true>(x);  // over m: Y[g][q]
 #pragma unroll
     for (int q = 1; q < 16; ++q) x[q] = cmul(x[q], tw[q]);
-    // transpose through LDS: row q, column g - real parts, then imaginary parts through the same 4.3 KB
-    float xre[16];
+    spec512_transpose_fft(x, xch, f, g);  // Z[g + 16 p] = x[p]; the exchange tile is reused for the power rows below
 #pragma unroll
-    for (int q = 0; q < 16; ++q) xch[(f * 16 + q) * XROW + g] = x[q].x;
-    air_wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 16; ++l) xre[l] = xch[(f * 16 + g) * XROW + l];
-    air_wave_lds_fence();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xch[(f * 16 + q) * XROW + g] = x[q].y;
-    air_wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 16; ++l) x[l] = cf{xre[l], xch[(f * 16 + g) * XROW + l]};
-    fft16<false>(x);  // over l: Z[g + 16 p] = x[p]
-    air_wave_lds_fence();  // exchange tile is reused for the power rows below
-
-    // real-FFT untangle + power.  Partner lane holds Z[(16-g)%16 + 16 p'].
-    float pnyq = 0.0f;
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      // bin k = g + 16 p pairs with 256 - k: lane (16-g)&15, index 15-p  (g != 0)
-      //                                      own lane, index (16-p)&15   (g == 0)
-      const int pp = 15 - p;
-      float bre = __shfl(x[pp].x, partner, 64);
-      float bim = __shfl(x[pp].y, partner, 64);
-      const int p0 = (16 - p) & 15;
-      if (g == 0) {
-        bre = x[p0].x;
-        bim = x[p0].y;
-      }
-      // E2 = A + conj(B), O2 = A - conj(B);  2X = E2 - i w512^k O2 - on register pairs (same roundings as the scalar
-      // form: xr = (ere + c oim) - s ore, xi = (eim - c ore) - s oim)
-      const cf A = x[p], Bv = cf{bre, bim};
-      const cf E = __builtin_elementwise_fma(Bv, cf{1.0f, -1.0f}, A);  // (A.re + bre, A.im - bim)
-      const cf O = __builtin_elementwise_fma(Bv, cf{-1.0f, 1.0f}, A);  // (A.re - bre, A.im + bim)
-      const cf cs = cmul(cf{cq, sq}, cf{W32C[p], W32S[p]});  // (cos, sin)(2 pi k / 512)
-      const cf P1 = LFCC_LO(cs) * LFCC_SWAP(O);              // (c oim, c ore)
-      const cf X1 = __builtin_elementwise_fma(P1, cf{1.0f, -1.0f}, E);
-      const cf X = X1 - LFCC_HI(cs) * O;                     // - (s ore, s oim)
-      const cf X2 = X * X;
-      const float xr2 = X2.x, xi2 = X2.y;
-      // reference: norm(.,2,-1).pow(2) (feature_extraction.py:113), i.e. fl(fl(sqrt(s))^2) - within 1.5 ulp of s itself.
-      // Round 5: the power is taken directly (X holds 2 x the bin: the factor 0.25 is exact); LFCC_EXACT_NORM = 1
-      // keeps the square root and the square (+ ~160 VALU instructions per wave for the correctly rounded sqrtf).
-#if LFCC_EXACT_NORM
-      const float mag = 0.5f * sqrtf(xr2 + xi2);
-      xch[f * PROW + g + 16 * p] = mag * mag;
-#else
-      xch[f * PROW + g + 16 * p] = 0.25f * (xr2 + xi2);
-#endif
-      if (p == 0) {
-        const float ny = x[0].x - x[0].y;  // X[256] = Re Z0 - Im Z0 (real)
-        pnyq = ny * ny;
-      }
-    }
-    if (g == 0) xch[f * PROW + 256] = pnyq;
+    for (int p = 0; p < 16; ++p) xch[f * PROW + g + 16 * p] = spec512_bin_power(x, p, g, ln);
+    if (g == 0) xch[f * PROW + 256] = spec512_nyquist_power(x);
     if (MW_C && g >= 1 && g < PROW - 256) xch[f * PROW + 256 + g] = 0.0f;  // zeros behind the Nyquist bin (below)
     air_wave_lds_fence();
 
@@ -330,7 +261,6 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
     air_wave_lds_fence();  // next group overwrites the exchange tile
   }
   __syncthreads();
-  if (RAGGED && LFCC_RAGGED_NOSKIP && dead) return;  // (A/B only: staged and computed, nothing to write)
 
   // ---- deltas into an LDS tile, then coalesced stores -----------------------
   // Round 5: a thread takes one coefficient of TWO neighbouring frames - six clamped cepstra c(t-2) .. c(t+3) give the
@@ -379,45 +309,10 @@ __device__ __forceinline__ void lfcc_body(const Args& a, float* __restrict__ s_p
   __syncthreads();
   if (!padded) {
     float* __restrict__ orow = a.out + ((size_t)b * T + t0) * D;
-    const int nvalid = min(FOUT, T - t0);
-    const int n = nvalid * D;
-    if ((D & 3) == 0 && ((reinterpret_cast<size_t>(orow) & 15) == 0)) {
-      for (int e = tid; e < n / 4; e += NTHREADS)
-        reinterpret_cast<float4*>(orow)[e] = reinterpret_cast<const float4*>(s_out)[e];
-    } else {
-      for (int e = tid; e < n; e += NTHREADS) orow[e] = s_out[e];
-    }
+    spec512_store_dense<NTHREADS>(orow, s_out, min(FOUT, T - t0) * D, D, tid);
   } else {
-    // (B, D, feat_len): frame t lands on t' = t - start (+ k T when repeating)
-    const int flen = a.feat_len;
-    // crop start clamped to the valid range: a bad offset must not leave columns unwritten
-    const int start = (a.start != nullptr && T > flen) ? min(max(a.start[b], 0), T - flen) : 0;
-    float* __restrict__ obase = a.out + (size_t)b * D * flen;
-    const int npad = flen - T;  // > 0: pad (dataset.py:72-79)
-    const int shift = (npad > 0 && a.pad_mode == AIR_PAD_SILENCE) ? npad : 0;  // silence is PREPENDED (:528)
-    for (int e = tid; e < FOUT * D; e += NTHREADS) {
-      const int c = e / FOUT, fo = e - c * FOUT;
-      const int t = t0 + fo;
-      if (t >= T) continue;
-      const float v = s_out[c * OSTR + fo];
-      if (T >= flen) {
-        const int tp = t - start;
-        if (tp >= 0 && tp < flen) obase[(size_t)c * flen + tp] = v;
-      } else if (a.pad_mode == AIR_PAD_REPEAT) {
-        for (int tp = t; tp < flen; tp += T) obase[(size_t)c * flen + tp] = v;
-      } else {
-        obase[(size_t)c * flen + t + shift] = v;
-      }
-    }
-    if (npad > 0 && a.pad_mode != AIR_PAD_REPEAT) {
-      // the npad constant frames (zeros appended, :513-517, or the silence frame prepended, :524-528),
-      // shared out over the utterance's tiles
-      const int lo = a.pad_mode == AIR_PAD_SILENCE ? 0 : T;
-      for (int e = tile * NTHREADS + tid; e < npad * D; e += live_tiles * NTHREADS) {
-        const int c = e / npad, k = e - c * npad;
-        obase[(size_t)c * flen + lo + k] = a.pad_mode == AIR_PAD_SILENCE ? a.silence[c] : 0.0f;
-      }
-    }
+    spec512_store_padded<FOUT, NTHREADS, true>(a.out + (size_t)b * D * a.feat_len, s_out, D, T, t0, tile, live_tiles,
+                                               a.feat_len, a.start, b, a.pad_mode, a.silence, tid);
   }
 }
 
@@ -501,14 +396,19 @@ __global__ __launch_bounds__(256) void pad_transpose_kernel(const float* feat, i
   }
 }
 
-int lfcc_launch(const float* pcm, const short* pcm16, int B, int L, float* out, int feat_len, const int* start,
-                const void* plan_dev, int flags, hipStream_t stream, int pad_mode = AIR_PAD_REPEAT,
-                const float* silence = nullptr) {
-  if ((!pcm && !pcm16) || !out || !plan_dev || B <= 0 || L <= 0) return AIR_EINVAL;
+// Fixed-length batch (lengths == nullptr): B rows of L samples, into (B, T, D) or, with FLAG_PADDED, (B, D, feat_len).
+// Ragged batch: B rows of capacity L, row b holding lengths[b] samples, into (B, D, feat_len); the grid covers a full row
+// for every utterance (B x ceil(Tcap / FOUT)), and what a shorter row does not need leaves at once (lfcc_body).
+int lfcc_launch(const float* pcm, const short* pcm16, int B, int L, const int* lengths, bool ragged, float* out,
+                int feat_len, const int* start, const void* plan_dev, int flags, hipStream_t stream,
+                int pad_mode = AIR_PAD_REPEAT, const float* silence = nullptr) {
+  if (ragged ? ((pcm != nullptr) == (pcm16 != nullptr) || !lengths || feat_len <= 0) : (!pcm && !pcm16)) return AIR_EINVAL;
+  if (!out || !plan_dev || B <= 0 || L <= 0) return AIR_EINVAL;
   if (pad_mode < AIR_PAD_REPEAT || pad_mode > AIR_PAD_SILENCE) return AIR_EINVAL;  // dataset.py:79 raises ValueError
   if (pad_mode == AIR_PAD_SILENCE && !silence) return AIR_EINVAL;
+  if (ragged) flags |= FLAG_PADDED;
   const int T = 1 + L / FS;
-  LfccArgs a;
+  LfccRaggedArgs a;
   a.pcm = pcm;
   a.pcm16 = pcm16;
   a.out = out;
@@ -521,47 +421,18 @@ int lfcc_launch(const float* pcm, const short* pcm16, int B, int L, float* out, 
   a.tiles = (T + FOUT - 1) / FOUT;
   a.flags = flags;
   a.feat_len = feat_len;
+  a.lengths = lengths;
   {
-    // algorithmic bytes: fp32 PCM in + fp32 features out
+    // algorithmic bytes: PCM in + fp32 features out.  A ragged batch's lengths live on the device, so
+    // its input is accounted at the row capacity, an upper bound on what the live tiles read
     const int nf = (flags & FLAG_DELTA) ? 3 : 1;
     const double out_frames = (flags & FLAG_PADDED) ? (double)feat_len : (double)T;
     AirProfScope ps(AIR_K_LFCC, B * ((pcm16 ? 2.0 : 4.0) * L + 4.0 * out_frames * nf * 20.0), stream);
-    hipLaunchKernelGGL(lfcc_kernel, dim3((unsigned)(B * a.tiles)), dim3(NTHREADS), 0, stream, a);
-  }
-  AIR_CHECK_LAUNCH();
-  return AIR_OK;
-}
-
-// Ragged batch: B rows of capacity Lcap, row b holding lengths[b] samples.  The grid covers a full row for every
-// utterance (B x ceil(Tcap / FOUT)); what a shorter row does not need leaves at once (lfcc_body).
-int lfcc_launch_ragged(const float* pcm, const short* pcm16, int B, int Lcap, const int* lengths, float* out,
-                       int feat_len, const int* start, const void* plan_dev, int flags, hipStream_t stream, int pad_mode,
-                       const float* silence) {
-  if ((pcm != nullptr) == (pcm16 != nullptr) || !lengths || !out || !plan_dev || B <= 0 || Lcap <= 0 || feat_len <= 0)
-    return AIR_EINVAL;
-  if (pad_mode < AIR_PAD_REPEAT || pad_mode > AIR_PAD_SILENCE) return AIR_EINVAL;
-  if (pad_mode == AIR_PAD_SILENCE && !silence) return AIR_EINVAL;
-  const int Tcap = 1 + Lcap / FS;
-  LfccRaggedArgs a;
-  a.pcm = pcm;
-  a.pcm16 = pcm16;
-  a.out = out;
-  a.plan = reinterpret_cast<const LfccPlan*>(plan_dev);
-  a.start = start;
-  a.silence = silence;
-  a.pad_mode = pad_mode;
-  a.L = Lcap;
-  a.T = Tcap;
-  a.tiles = (Tcap + FOUT - 1) / FOUT;
-  a.flags = flags | FLAG_PADDED;
-  a.feat_len = feat_len;
-  a.lengths = lengths;
-  {
-    // algorithmic bytes: the lengths live on the device, so the input is accounted at the row capacity Lcap (an upper
-    // bound on what the live tiles read) + the fp32 features out
-    const int nf = (flags & FLAG_DELTA) ? 3 : 1;
-    AirProfScope ps(AIR_K_LFCC, B * ((pcm16 ? 2.0 : 4.0) * Lcap + 4.0 * (double)feat_len * nf * 20.0), stream);
-    hipLaunchKernelGGL(lfcc_ragged_kernel, dim3((unsigned)(B * a.tiles)), dim3(NTHREADS), 0, stream, a);
+    const dim3 grid((unsigned)(B * a.tiles));
+    if (ragged)
+      hipLaunchKernelGGL(lfcc_ragged_kernel, grid, dim3(NTHREADS), 0, stream, a);
+    else
+      hipLaunchKernelGGL(lfcc_kernel, grid, dim3(NTHREADS), 0, stream, static_cast<const LfccArgs&>(a));
   }
   AIR_CHECK_LAUNCH();
   return AIR_OK;
@@ -585,17 +456,11 @@ int air_lfcc_plan_build(const float* fb_host, int nbin, int nfilt, const float* 
   p->fs = fs;
   p->fn = fn;
   p->nbin = nbin;
-  const double pi = 3.14159265358979323846;
-  for (int n = 0; n < FL; ++n)
-    p->window[n] = window_host ? window_host[n] : (float)(0.54 - 0.46 * cos(2.0 * pi * n / FL));
-  for (int n = 0; n < 256; ++n) {
-    p->tw256[2 * n] = (float)cos(2.0 * pi * n / 256.0);
-    p->tw256[2 * n + 1] = (float)(-sin(2.0 * pi * n / 256.0));
-  }
-  for (int q = 0; q < 16; ++q) {
-    p->tw512[2 * q] = (float)cos(2.0 * pi * q / 512.0);
-    p->tw512[2 * q + 1] = (float)(-sin(2.0 * pi * q / 512.0));
-  }
+  if (window_host)
+    memcpy(p->window, window_host, sizeof(p->window));
+  else
+    spec512_fill_hamming(p->window, FL);
+  spec512_fill_twiddles(p->tw256, p->tw512);
   int maxw = 1;
   for (int j = 0; j < nfilt; ++j) {
     int first = -1, last = -1;
@@ -630,7 +495,7 @@ int air_lfcc_plan_build(const float* fb_host, int nbin, int nfilt, const float* 
 
 int air_lfcc_fwd(const float* pcm, int B, int L, float* out, const void* plan_dev, int flags,
                  air_stream_t stream) {
-  return lfcc_launch(pcm, nullptr, B, L, out, 0, nullptr, plan_dev,
+  return lfcc_launch(pcm, nullptr, B, L, nullptr, false, out, 0, nullptr, plan_dev,
                      flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA), air_stream(stream));
 }
 
@@ -638,7 +503,7 @@ int air_lfcc_fwd_padded(const float* pcm, int B, int L, float* out, int feat_len
                         const int* start_dev, const void* plan_dev, int flags,
                         air_stream_t stream) {
   if (feat_len <= 0) return AIR_EINVAL;
-  return lfcc_launch(pcm, nullptr, B, L, out, feat_len, start_dev, plan_dev,
+  return lfcc_launch(pcm, nullptr, B, L, nullptr, false, out, feat_len, start_dev, plan_dev,
                      (flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA)) | FLAG_PADDED,
                      air_stream(stream));
 }
@@ -647,7 +512,7 @@ int air_lfcc_fwd_padded_ex(const float* pcm, const int16_t* pcm16, int B, int L,
                            const int* start_dev, const void* plan_dev, int flags, int pad_mode,
                            const float* silence_dev, air_stream_t stream) {
   if (feat_len <= 0 || (pcm != nullptr) == (pcm16 != nullptr)) return AIR_EINVAL;
-  return lfcc_launch(pcm, reinterpret_cast<const short*>(pcm16), B, L, out, feat_len, start_dev, plan_dev,
+  return lfcc_launch(pcm, reinterpret_cast<const short*>(pcm16), B, L, nullptr, false, out, feat_len, start_dev, plan_dev,
                      (flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA)) | FLAG_PADDED, air_stream(stream), pad_mode,
                      silence_dev);
 }
@@ -655,15 +520,14 @@ int air_lfcc_fwd_padded_ex(const float* pcm, const int16_t* pcm16, int B, int L,
 int air_lfcc_fwd_ragged(const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev, float* out,
                         int feat_len, const int* start_dev, const void* plan_dev, int flags, int pad_mode,
                         const float* silence_dev, air_stream_t stream) {
-  return lfcc_launch_ragged(pcm, reinterpret_cast<const short*>(pcm16), B, Lcap, lengths_dev, out, feat_len, start_dev,
-                            plan_dev, flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA), air_stream(stream), pad_mode,
-                            silence_dev);
+  return lfcc_launch(pcm, reinterpret_cast<const short*>(pcm16), B, Lcap, lengths_dev, true, out, feat_len, start_dev,
+                     plan_dev, flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA), air_stream(stream), pad_mode, silence_dev);
 }
 
 int air_lfcc_fwd_padded_i16(const int16_t* pcm16, int B, int L, float* out, int feat_len,
                             const int* start_dev, const void* plan_dev, int flags, air_stream_t stream) {
   // feat_len <= 0: the (B, T, D) layout of air_lfcc_fwd
-  return lfcc_launch(nullptr, reinterpret_cast<const short*>(pcm16), B, L, out, feat_len > 0 ? feat_len : 0,
+  return lfcc_launch(nullptr, reinterpret_cast<const short*>(pcm16), B, L, nullptr, false, out, feat_len > 0 ? feat_len : 0,
                      start_dev, plan_dev,
                      (flags & (AIR_LFCC_EMPHASIS | AIR_LFCC_DELTA)) | (feat_len > 0 ? FLAG_PADDED : 0),
                      air_stream(stream));

@@ -9,9 +9,10 @@
 //
 // Mapping (wave64), as in csrc/lfcc.hip: 16 lanes per frame, 4 frames per wave, 8 waves per workgroup.  There are no
 // deltas, hence no halo: a workgroup computes and writes the same 32 frames.  The 512-point real FFT is a 256-point
-// complex FFT on the even/odd packing, done as 16 x 16 with the radix-16 butterfly of air_fft16.h, the transpose through
-// a padded wave-private LDS tile and the real-FFT untangle against lane (16 - g) of the same 16-lane group (the window /
-// transpose / untangle are restated here: lfcc.hip's bits are pinned and that file is left alone).  The STFT window sits
+// complex FFT on the even/odd packing, done as 16 x 16 with the radix-16 butterfly of air_fft16.h.  The PCM staging, the
+// transpose through a padded wave-private LDS tile, the real-FFT untangle against lane (16 - g) of the same 16-lane
+// group, the ragged row geometry and both copy-outs are the pieces of air_spec512.h, shared with the LFCC kernel; the
+// window (read from the plan at use), the tile overlay and the mel filterbank are this file's own.  The STFT window sits
 // at offset 0 of the frame instead of 96: a phase only, which |X|^2 discards.
 //
 // LDS: every wave handles ONE 4-frame group, so the staged PCM is dead once each lane holds its 16 windowed samples - a
@@ -23,8 +24,7 @@
 #include <string.h>
 
 #include "air_common.h"
-#include "air_fft16.h"
-#include "air_pcm.h"
+#include "air_spec512.h"
 
 namespace {
 
@@ -33,9 +33,8 @@ constexpr int NBIN = FN / 2 + 1;      // 257
 constexpr int NW = 8;                 // waves per workgroup
 constexpr int NTHREADS = NW * 64;
 constexpr int FT = 4 * NW;            // 32 frames computed and written per workgroup
-constexpr int XROW = 17;              // padded transpose row (complex elements)
 constexpr int PROW = 264;             // MEL: power-spectrum row stride; zeros behind the Nyquist bin
-constexpr int XCH_FLOATS = 4 * 16 * XROW;  // wave-private: the 4 x 16 x 17 transposition, then (MEL) 4 power rows
+constexpr int XCH_FLOATS = 4 * 16 * SPEC512_XROW;  // wave-private: the 4 x 16 x 17 transposition, then (MEL) 4 power rows
 static_assert(4 * PROW <= XCH_FLOATS, "power rows must fit the exchange tile");
 constexpr int OSTR = FT + 1;          // (B, D, feat_len) layout: s_out[c][fo], odd stride
 constexpr int NMEL = 128;             // mel bands: 8 per lane of a 16-lane frame group
@@ -50,15 +49,6 @@ struct SpecPlan {
   int cnt[NMEL];              // MEL: bins spanned by filter j
   float fbwT[MELW * NMEL];    // MEL: [i][j] = weight of bin lo[j] + i in filter j
 };
-
-__device__ __constant__ const float W32C[16] = {
-    1.000000000f, 0.980785280f, 0.923879533f, 0.831469612f, 0.707106781f, 0.555570233f,
-    0.382683432f, 0.195090322f, 0.000000000f, -0.195090322f, -0.382683432f, -0.555570233f,
-    -0.707106781f, -0.831469612f, -0.923879533f, -0.980785280f};
-__device__ __constant__ const float W32S[16] = {
-    0.000000000f, 0.195090322f, 0.382683432f, 0.555570233f, 0.707106781f, 0.831469612f,
-    0.923879533f, 0.980785280f, 1.000000000f, 0.980785280f, 0.923879533f, 0.831469612f,
-    0.707106781f, 0.555570233f, 0.382683432f, 0.195090322f};
 
 template <int KIND>
 struct Geo;
@@ -111,73 +101,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void spec_kernel(SpecArgs a) {
   int L = a.L, T = a.T;
   int live_tiles = a.tiles;  // tiles of this row that write frames: they share the row's zero frames
   if constexpr (PADDED) {
-    if (a.lengths != nullptr) L = min(max(a.lengths[b], 1), a.L);  // a bad length in device memory stays inside the row
-    T = 1 + L / HOP;
-    live_tiles = (T + FT - 1) / FT;
-    bool dead = t0 >= T;  // this tile holds no frame that the row writes
-    if (T > a.feat_len) {
-      // chopped row: only the tiles that overlap [start, start + feat_len) are written (same clamp as below)
-      const int st = a.start != nullptr ? min(max(a.start[b], 0), T - a.feat_len) : 0;
-      dead = dead || t0 + FT <= st || t0 >= st + a.feat_len;
-    }
-    if (dead) return;  // (workgroup-uniform, ahead of every barrier and of the staging)
+    const Spec512Row r = spec512_row<HOP, FT, true>(a.lengths, a.start, b, a.L, a.feat_len, t0);
+    if (r.dead) return;  // (workgroup-uniform, ahead of every barrier and of the staging)
+    L = r.L;
+    T = r.T;
+    live_tiles = r.live_tiles;
   }
   const float* __restrict__ row = a.pcm ? a.pcm + (size_t)b * a.L : nullptr;
   const short* __restrict__ row16 = a.pcm16 ? a.pcm16 + (size_t)b * a.L : nullptr;
-  auto sample = [&](long m) -> float { return row16 ? air_pcm_sample(row16, m) : row[m]; };
 
   // ---- stage the filter weights and the PCM --------------------------------
   if constexpr (MEL) {
     for (int e = tid; e < MELW * NMEL; e += NTHREADS) s_fbw[e] = plan->fbwT[e];
   }
   const long s0 = (long)HOP * t0 - G::LEAD;  // first staged sample (may be < 0); a multiple of 4
-  const bool emph = !MEL && (a.flags & FLAG_EMPH) != 0;
-  const bool reflect = MEL && (a.flags & FLAG_REFLECT) != 0;
-  const bool vec_ok = row16 == nullptr && ((((size_t)row) & 15) == 0);
-  for (int e4 = tid; e4 < NSAMP / 4; e4 += NTHREADS) {
-    const long n = s0 + 4 * (long)e4;
-    float v[4];
-    if (vec_ok && n >= 0 && n + 3 < L) {
-      const float4 q = *reinterpret_cast<const float4*>(row + n);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-      if (emph) {
-        const float prev = n > 0 ? row[n - 1] : 0.0f;
-        // non-recursive FIR on the ORIGINAL samples, two roundings like the reference (:157)
-        v[3] = __fsub_rn(v[3], __fmul_rn(0.97f, v[2]));
-        v[2] = __fsub_rn(v[2], __fmul_rn(0.97f, v[1]));
-        v[1] = __fsub_rn(v[1], __fmul_rn(0.97f, v[0]));
-        if (n > 0) v[0] = __fsub_rn(v[0], __fmul_rn(0.97f, prev));
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        long m = n + k;
-        float x = 0.0f;
-        if (reflect) {
-          // numpy's "reflect": x[-m] in front, x[2 (L - 1) - m] behind; one reflection, then clamped into the row - what
-          // a frame of a row of at least 257 samples reads is never clamped, and nothing can read outside a shorter one
-          if (m < 0) m = -m;
-          else if (m >= L) m = 2 * ((long)L - 1) - m;
-          m = m < 0 ? 0 : (m > L - 1 ? L - 1 : m);
-          x = sample(m);
-        } else if (m >= 0 && m < L) {
-          x = sample(m);
-          if (emph && m > 0) x = __fsub_rn(x, __fmul_rn(0.97f, sample(m - 1)));
-        }
-        v[k] = x;
-      }
-    }
-    *reinterpret_cast<float4*>(&s_main[4 * e4]) = make_float4(v[0], v[1], v[2], v[3]);
-  }
+  spec512_stage<NSAMP, NTHREADS, MEL>(row, row16, L, s0, !MEL && (a.flags & FLAG_EMPH) != 0,
+                                      MEL && (a.flags & FLAG_REFLECT) != 0, s_main, tid);
 
   // ---- per-lane constants --------------------------------------------------
   const int f = lane >> 4;       // frame within the wave's 4-frame group
   const int g = lane & 15;       // lane within the frame
   const int fi = wave * 4 + f;   // frame within the tile
   const bool active = t0 + wave * 4 < T;  // wave-uniform: the group holds a frame of the row
-  const float cq = plan->tw512[2 * g];        //  cos(2 pi g/512)
-  const float sq = -plan->tw512[2 * g + 1];   //  sin(2 pi g/512)
-  const int partner = (lane & 48) | ((16 - g) & 15);
+  const Spec512Lane ln = spec512_lane(plan->tw512, lane);
   float* xch = s_xch + wave * XCH_FLOATS;
 
   __syncthreads();
@@ -204,21 +150,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void spec_kernel(SpecArgs a) {
       const int n = (g * q) & 255;
       x[q] = cmul(x[q], cf{plan->tw256[2 * n], plan->tw256[2 * n + 1]});  // w256^(g q)
     }
-    // transpose through LDS: row q, column g - real parts, then imaginary parts through the same 4.3 KB
-    float xre[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xch[(f * 16 + q) * XROW + g] = x[q].x;
-    air_wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 16; ++l) xre[l] = xch[(f * 16 + g) * XROW + l];
-    air_wave_lds_fence();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) xch[(f * 16 + q) * XROW + g] = x[q].y;
-    air_wave_lds_fence();
-#pragma unroll
-    for (int l = 0; l < 16; ++l) x[l] = cf{xre[l], xch[(f * 16 + g) * XROW + l]};
-    fft16<false>(x);  // over l: Z[g + 16 p] = x[p]
-    air_wave_lds_fence();  // MEL: the exchange tile is reused for the power rows below
+    spec512_transpose_fft(x, xch, f, g);  // Z[g + 16 p] = x[p]; MEL: the exchange tile is reused for the power rows below
 
     // where bin k of this lane's frame goes: the output tile (STFT) or the wave's power row (MEL)
     auto put = [&](int k, float pw) {
@@ -226,38 +158,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void spec_kernel(SpecArgs a) {
       else if constexpr (PADDED) s_out[k * OSTR + fi] = pw;
       else s_out[fi * D + k] = pw;
     };
-    // real-FFT untangle + power.  Partner lane holds Z[(16-g)%16 + 16 p'].
-    float pnyq = 0.0f;
 #pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      // bin k = g + 16 p pairs with 256 - k: lane (16-g)&15, index 15-p  (g != 0)
-      //                                      own lane, index (16-p)&15   (g == 0)
-      const int pp = 15 - p;
-      float bre = __shfl(x[pp].x, partner, 64);
-      float bim = __shfl(x[pp].y, partner, 64);
-      const int p0 = (16 - p) & 15;
-      if (g == 0) {
-        bre = x[p0].x;
-        bim = x[p0].y;
-      }
-      // E2 = A + conj(B), O2 = A - conj(B);  2X = E2 - i w512^k O2
-      const cf A = x[p], Bv = cf{bre, bim};
-      const cf E = __builtin_elementwise_fma(Bv, cf{1.0f, -1.0f}, A);  // (A.re + bre, A.im - bim)
-      const cf O = __builtin_elementwise_fma(Bv, cf{-1.0f, 1.0f}, A);  // (A.re - bre, A.im + bim)
-      const cf cs = cmul(cf{cq, sq}, cf{W32C[p], W32S[p]});  // (cos, sin)(2 pi k / 512)
-      const cf P1 = LFCC_LO(cs) * LFCC_SWAP(O);              // (c oim, c ore)
-      const cf X1 = __builtin_elementwise_fma(P1, cf{1.0f, -1.0f}, E);
-      const cf X = X1 - LFCC_HI(cs) * O;                     // - (s ore, s oim)
-      const cf X2 = X * X;
-      // the reference takes norm(., 2, -1).pow(2) (:163), fl(fl(sqrt(s))^2), within 1.5 ulp of s itself; the power is
-      // taken directly (X holds 2 x the bin: the factor 0.25 is exact)
-      put(g + 16 * p, 0.25f * (X2.x + X2.y));
-      if (p == 0) {
-        const float ny = x[0].x - x[0].y;  // X[256] = Re Z0 - Im Z0 (real)
-        pnyq = ny * ny;
-      }
-    }
-    if (g == 0) put(256, pnyq);
+    for (int p = 0; p < 16; ++p) put(g + 16 * p, spec512_bin_power(x, p, g, ln));
+    if (g == 0) put(256, spec512_nyquist_power(x));
 
     if constexpr (MEL) {
       if (g >= 1 && g < PROW - 256) xch[f * PROW + 256 + g] = 0.0f;  // zeros behind the Nyquist bin
@@ -281,41 +184,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void spec_kernel(SpecArgs a) {
   // ---- coalesced stores ------------------------------------------------------
   if constexpr (!PADDED) {
     float* __restrict__ orow = a.out + ((size_t)b * T + t0) * D;
-    const int n = min(FT, T - t0) * D;
-    if ((D & 3) == 0 && ((reinterpret_cast<size_t>(orow) & 15) == 0)) {
-      for (int e = tid; e < n / 4; e += NTHREADS)
-        reinterpret_cast<float4*>(orow)[e] = reinterpret_cast<const float4*>(s_out)[e];
-    } else {
-      for (int e = tid; e < n; e += NTHREADS) orow[e] = s_out[e];
-    }
+    spec512_store_dense<NTHREADS>(orow, s_out, min(FT, T - t0) * D, D, tid);
   } else {
-    // (B, D, feat_len): frame t lands on t' = t - start (+ k T when repeating); a 32-lane run is one bin's 32 frames
-    const int flen = a.feat_len;
-    // crop start clamped to the valid range: a bad offset must not leave columns unwritten
-    const int start = (a.start != nullptr && T > flen) ? min(max(a.start[b], 0), T - flen) : 0;
-    float* __restrict__ obase = a.out + (size_t)b * D * flen;
-    const int npad = flen - T;  // > 0: pad (dataset.py:72-79)
-    for (int e = tid; e < FT * D; e += NTHREADS) {
-      const int c = e / FT, fo = e - c * FT;
-      const int t = t0 + fo;
-      if (t >= T) continue;
-      const float v = s_out[c * OSTR + fo];
-      if (T >= flen) {
-        const int tp = t - start;
-        if (tp >= 0 && tp < flen) obase[(size_t)c * flen + tp] = v;
-      } else if (a.pad_mode == AIR_PAD_REPEAT) {
-        for (int tp = t; tp < flen; tp += T) obase[(size_t)c * flen + tp] = v;
-      } else {
-        obase[(size_t)c * flen + t] = v;
-      }
-    }
-    if (npad > 0 && a.pad_mode == AIR_PAD_ZERO) {
-      // the npad zero frames appended (dataset.py:513-517), shared out over the row's live tiles
-      for (int e = tile * NTHREADS + tid; e < npad * D; e += live_tiles * NTHREADS) {
-        const int c = e / npad, k = e - c * npad;
-        obase[(size_t)c * flen + T + k] = 0.0f;
-      }
-    }
+    // (a 32-lane run of the copy-out is one bin's 32 frames)
+    spec512_store_padded<FT, NTHREADS, false>(a.out + (size_t)b * D * a.feat_len, s_out, D, T, t0, tile, live_tiles,
+                                              a.feat_len, a.start, b, a.pad_mode, nullptr, tid);
   }
 }
 
@@ -374,17 +247,12 @@ int air_spec_plan_build(int kind, void* plan_host_out) {
   p->hop = mel ? Geo<AIR_SPEC_MEL>::HOP : Geo<AIR_SPEC_STFT>::HOP;
   p->wlen = mel ? FN : 320;
   p->nbin = NBIN;
-  const double pi = 3.14159265358979323846;
-  for (int n = 0; n < p->wlen; ++n)  // periodic Hann (librosa's default window) / periodic Hamming (torch.hamming_window, :160)
-    p->window[n] = mel ? (float)(0.5 - 0.5 * cos(2.0 * pi * n / FN)) : (float)(0.54 - 0.46 * cos(2.0 * pi * n / 320.0));
-  for (int n = 0; n < 256; ++n) {
-    p->tw256[2 * n] = (float)cos(2.0 * pi * n / 256.0);
-    p->tw256[2 * n + 1] = (float)(-sin(2.0 * pi * n / 256.0));
+  if (mel) {
+    for (int n = 0; n < FN; ++n) p->window[n] = (float)(0.5 - 0.5 * cos(2.0 * SPEC512_PI * n / FN));  // periodic Hann (librosa's default)
+  } else {
+    spec512_fill_hamming(p->window, 320);  // torch.hamming_window (:160); taps 320 .. 511 stay zero
   }
-  for (int q = 0; q < 16; ++q) {
-    p->tw512[2 * q] = (float)cos(2.0 * pi * q / 512.0);
-    p->tw512[2 * q + 1] = (float)(-sin(2.0 * pi * q / 512.0));
-  }
+  spec512_fill_twiddles(p->tw256, p->tw512);
   if (!mel) return AIR_OK;
   // librosa.filters.mel(sr=16000, n_fft=512, n_mels=128, fmin=0, fmax=8000, htk=False, norm='slaney') in fp64:
   // fftfreqs = linspace(0, 8000, 257), mel_f = mel_to_hz(linspace(0, hz_to_mel(8000), 130))

@@ -1,10 +1,11 @@
-"""Drop-ins for the reference's front-ends: ``LFCC`` (feature_extraction.py:61-138) and, at the end of this file,
-``STFT`` (:141-165) and ``Melspec`` (:168-176) on the kernels of csrc/spectral.hip.
+"""Drop-ins for the reference's front-ends: ``LFCC`` (feature_extraction.py:61-138) on the kernel of csrc/lfcc.hip,
+``STFT`` (:141-165) and ``Melspec`` (:168-176) on the kernels of csrc/spectral.hip.  What the three share on the host -
+plan cache, input checks, output allocation, the padded / ragged call - is ``_FrontEnd``.
 
-Same constructor, same ``forward(x:(B,L)) -> (B, 1+L//fs, 3*filter_num)``,
+``LFCC``: same constructor, same ``forward(x:(B,L)) -> (B, 1+L//fs, 3*filter_num)``,
 same ``state_dict`` keys (``lfcc_fb``, ``l_dct.weight``), same in-place
 pre-emphasis of the caller's tensor (:106).  The device work is ONE fused HIP
-kernel (csrc/lfcc.hip) reached through ``air_lfcc_fwd``.
+kernel reached through ``air_lfcc_fwd``.
 """
 import math
 
@@ -85,8 +86,106 @@ def _pcm_source(x):
     return x.float().contiguous()
 
 
-class LFCC(nn.Module):
+def preemph_inplace_(x):
+    """x[:, 1:] -= 0.97 * x[:, :-1] on the original samples, in place (feature_extraction.py:106, :157)."""
+    lib = _hip.lib()
+    B, L = x.shape
+    nbytes = lib.air_preemph_ws_bytes(_hip.ci(B), _hip.ci(L))
+    ws = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
+    _hip.check(lib.air_preemph_inplace(_hip.dptr(x), _hip.ci(B), _hip.ci(L), _hip.cf(0.97),
+                                       _hip.dptr(ws), _hip.csz(nbytes), _hip.stream()),
+               "air_preemph_inplace")
+
+
+class _FrontEnd(nn.Module):
+    """What the three PCM front-ends share on the host: the cached plan blob, the input checks, the ``start`` upload, the
+    output allocation around the dense and the padded / ragged call, and the reference's in-place pre-emphasis of the
+    caller's tensor.  A subclass supplies ``NAME``, ``out_dim``, ``fs`` (the hop), ``_flags()``, its plan
+    (``_plan_id`` / ``_plan_build``), its C entry points (``_call_dense`` / ``_call_padded``) and ``_check``."""
+    NAME = "?"
+
+    def __init__(self):
+        super().__init__()
+        self._plan = None
+        self._plan_key = None
+
+    def _plan_id(self, device):
+        """What the cached plan depends on."""
+        return str(device)
+
+    def plan(self, device):
+        """Device-resident plan blob (window, twiddles, filterbank; LFCC: DCT)."""
+        key = self._plan_id(device)
+        if self._plan is None or self._plan_key != key:
+            self._plan = self._plan_build(_hip.lib()).to(device)
+            self._plan_key = key
+        return self._plan
+
+    def _check_x(self, x):
+        if x.dim() != 2:
+            raise ValueError("%s expects (batch, length), got %s" % (self.NAME, tuple(x.shape)))
+        if not x.is_cuda:
+            raise _hip.AirError("%s HIP path needs a GPU tensor; there is no CPU fallback" % self.NAME)
+
+    def _check_lengths(self, host, Lcap):
+        """Host-side lengths beyond the [1, Lcap] check of ``ragged.device_lengths``."""
+
+    def _dense(self, x):
+        """(B, L) float32 or int16 on the GPU -> ((B, T, out_dim), the tensor the kernel read).  Does not mutate ``x``."""
+        B, L = x.shape
+        self._check_lengths(torch.tensor([L]), L)
+        src = _pcm_source(x)
+        out = torch.empty((B, 1 + L // self.fs, self.out_dim), device=x.device, dtype=torch.float32)
+        self._call_dense(_hip.lib(), src, _hip.ci(B), _hip.ci(L), _hip.dptr(out),
+                         _hip.dptr(self.plan(x.device), torch.uint8), _hip.ci(self._flags()))
+        return out, src
+
+    def _emphasise(self, x, src):
+        """The reference emphasises the caller's tensor in place; the kernel read the original samples, so this follows
+        it.  (Integers: nothing to mutate - the reference never sees them.)"""
+        if self.with_emphasis and self.mutate_input and x.dtype != torch.int16:
+            preemph_inplace_(src)
+            if src is not x:
+                x.copy_(src)
+
+    def _padded(self, x, lengths, feat_len, start, mode):
+        B, Lcap = x.shape
+        if start is not None and not (torch.is_tensor(start) and start.is_cuda):
+            start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
+        src = _pcm_source(x)
+        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
+        # (pcm, pcm16, B, L), the row lengths or None, (out, feat_len, start, plan, flags, pad_mode)
+        self._call_padded(_hip.lib(), (*pcm_pointers(src), _hip.ci(B), _hip.ci(Lcap)), lengths,
+                          (_hip.dptr(out), _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
+                           _hip.dptr(self.plan(x.device), torch.uint8), _hip.ci(self._flags()), _hip.ci(mode)),
+                          mode, x.device)
+        return out
+
+    def forward_padded(self, x, feat_len=750, start=None, padding="repeat"):
+        """Fused front-end -> pad / chop -> transpose: (B, L) -> (B, out_dim, feat_len), i.e. what dataset.py:62-79 +
+        main_train.py:338 build on the host.  Does not mutate ``x``.  ``start``: optional int32 (B,) crop offsets for
+        T > feat_len.  ``padding``: the reference's ``--padding`` choices 'repeat' | 'zero' | 'silence'
+        (main_train.py:45; 'silence' is LFCC's alone, NotImplementedError elsewhere); anything else raises ValueError
+        like dataset.py:79."""
+        mode = self._check(x, padding)
+        self._check_lengths(torch.tensor([x.shape[1]]), x.shape[1])
+        return self._padded(x, None, feat_len, start, mode)
+
+    def forward_ragged(self, x, lengths, feat_len=750, start=None, padding="repeat"):
+        """A batch of utterances of DIFFERENT lengths in one launch: ``x`` (B, Lcap) float32 or int16 on the GPU, row b
+        holding ``lengths[b]`` samples (what follows them is never read) -> (B, out_dim, feat_len), row b being what
+        ``forward_padded`` gives for that utterance alone.  Does not mutate ``x``.  ``lengths``: int32 (B,); a GPU tensor is
+        used as is (the kernel clamps it to [1, Lcap]), a host tensor or list is checked (ValueError) and uploaded.
+        ``start`` / ``padding``: as in ``forward_padded``, each row's offset clamped to its own [0, T_b - feat_len]."""
+        mode = self._check(x, padding)
+        B, Lcap = x.shape
+        lengths = device_lengths(lengths, B, Lcap, x.device, extra_check=self._check_lengths)
+        return self._padded(x, lengths, feat_len, start, mode)
+
+
+class LFCC(_FrontEnd):
     """LFCC(fl, fs, fn, sr, filter_num, with_energy=False, with_emphasis=True, with_delta=True)."""
+    NAME = "LFCC"
 
     def __init__(self, fl, fs, fn, sr, filter_num, with_energy=False, with_emphasis=True,
                  with_delta=True):
@@ -103,8 +202,6 @@ class LFCC(nn.Module):
         self.with_emphasis = with_emphasis
         self.with_delta = with_delta
         self.mutate_input = True  # reference behaviour (feature_extraction.py:106)
-        self._plan = None
-        self._plan_key = None
 
     @property
     def out_dim(self):
@@ -113,50 +210,48 @@ class LFCC(nn.Module):
     def _flags(self):
         return (1 if self.with_emphasis else 0) | (2 if self.with_delta else 0)
 
-    def plan(self, device):
-        """Device-resident plan blob (window, twiddles, sparse filterbank, DCT)."""
-        key = (str(device), self.lfcc_fb._version, self.l_dct.weight._version,
-               self.lfcc_fb.data_ptr(), self.l_dct.weight.data_ptr())
-        if self._plan is None or self._plan_key != key:
-            L = _hip.lib()
-            nbytes = L.air_lfcc_plan_bytes()
-            host = torch.zeros(nbytes, dtype=torch.uint8)
-            fb = self.lfcc_fb.detach().float().cpu().contiguous()
-            dct = self.l_dct.weight.detach().float().cpu().contiguous()
-            win = torch.hamming_window(self.fl).contiguous()
-            _hip.check(L.air_lfcc_plan_build(_hip.hptr(fb), _hip.ci(fb.shape[0]), _hip.ci(fb.shape[1]),
-                                             _hip.hptr(dct), _hip.hptr(win), _hip.ci(self.fl),
-                                             _hip.ci(self.fs), _hip.ci(self.fn),
-                                             _hip.hptr(host, torch.uint8)), "air_lfcc_plan_build")
-            self._plan = host.to(device)
-            self._plan_key = key
-        return self._plan
+    def _plan_id(self, device):
+        return (str(device), self.lfcc_fb._version, self.l_dct.weight._version,
+                self.lfcc_fb.data_ptr(), self.l_dct.weight.data_ptr())
 
-    def _check(self, x):
+    def _plan_build(self, lib):
+        host = torch.zeros(lib.air_lfcc_plan_bytes(), dtype=torch.uint8)
+        fb = self.lfcc_fb.detach().float().cpu().contiguous()
+        dct = self.l_dct.weight.detach().float().cpu().contiguous()
+        win = torch.hamming_window(self.fl).contiguous()
+        _hip.check(lib.air_lfcc_plan_build(_hip.hptr(fb), _hip.ci(fb.shape[0]), _hip.ci(fb.shape[1]),
+                                           _hip.hptr(dct), _hip.hptr(win), _hip.ci(self.fl),
+                                           _hip.ci(self.fs), _hip.ci(self.fn),
+                                           _hip.hptr(host, torch.uint8)), "air_lfcc_plan_build")
+        return host
+
+    def _check(self, x, padding="repeat"):
         if self.with_energy:
             raise NotImplementedError("with_energy=True is not on the hot path (dead branch, "
                                       "feature_extraction.py:123-127)")
-        if x.dim() != 2:
-            raise ValueError("LFCC expects (batch, length), got %s" % (tuple(x.shape),))
-        if not x.is_cuda:
-            raise _hip.AirError("LFCC HIP path needs a GPU tensor; there is no CPU fallback")
+        self._check_x(x)
+        return pad_mode_id(padding)
+
+    def _call_dense(self, lib, src, B, L, out, plan, flags):
+        if src.dtype == torch.int16:  # 16-bit PCM straight from the wav/flac samples (x = s / 32768 inside the kernel)
+            no_start = _hip.dptr(None, torch.int32, True)  # (feat_len 0: the (B, T, D) layout of air_lfcc_fwd)
+            _hip.check(lib.air_lfcc_fwd_padded_i16(_hip.dptr(src, torch.int16), B, L, out, _hip.ci(0), no_start, plan, flags,
+                                                   _hip.stream()), "air_lfcc_fwd_padded_i16")
+        else:
+            _hip.check(lib.air_lfcc_fwd(_hip.dptr(src), B, L, out, plan, flags, _hip.stream()), "air_lfcc_fwd")
+
+    def _call_padded(self, lib, rows, lengths, tail, mode, device):
+        sil = _hip.dptr(self.silence_row(device) if mode == 2 else None, allow_none=True)
+        if lengths is None:
+            _hip.check(lib.air_lfcc_fwd_padded_ex(*rows, *tail, sil, _hip.stream()), "air_lfcc_fwd_padded_ex")
+        else:
+            _hip.check(lib.air_lfcc_fwd_ragged(*rows, _hip.dptr(lengths, torch.int32), *tail, sil, _hip.stream()),
+                       "air_lfcc_fwd_ragged")
 
     def forward(self, x):
         self._check(x)
-        B, L = x.shape
-        if x.dtype == torch.int16:  # raw 16-bit PCM: nothing to mutate (the reference never sees integers)
-            return self._forward_i16(x, 0, None)
-        T = 1 + L // self.fs
-        src = _pcm_source(x)
-        out = torch.empty((B, T, self.out_dim), device=x.device, dtype=torch.float32)
-        lib = _hip.lib()
-        _hip.check(lib.air_lfcc_fwd(_hip.dptr(src), _hip.ci(B), _hip.ci(L), _hip.dptr(out),
-                                    _hip.dptr(self.plan(x.device), torch.uint8),
-                                    _hip.ci(self._flags()), _hip.stream()), "air_lfcc_fwd")
-        if self.with_emphasis and self.mutate_input:
-            self._preemph_inplace(src)
-            if src is not x:
-                x.copy_(src)
+        out, src = self._dense(x)
+        self._emphasise(x, src)
         return out
 
     def silence_row(self, device):
@@ -172,163 +267,35 @@ class LFCC(nn.Module):
             self._silence, self._silence_key = row, (str(device), self._plan_key)
         return self._silence
 
-    def forward_padded(self, x, feat_len=750, start=None, padding="repeat"):
-        """Fused LFCC -> pad/chop -> transpose: (B, L) -> (B, out_dim, feat_len), i.e. what
-        dataset.py:66-79 + main_train.py:338 build on the host.  Does not mutate ``x``.
-        ``start``: optional int32 (B,) crop offsets for T > feat_len.  ``padding``: the reference's
-        ``--padding`` choices 'repeat' | 'zero' | 'silence' (main_train.py:45); anything else raises
-        ValueError like dataset.py:79."""
-        self._check(x)
-        mode = pad_mode_id(padding)
-        B, L = x.shape
-        src = _pcm_source(x)
-        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
-        sil = self.silence_row(x.device) if mode == 2 else None
-        lib = _hip.lib()
-        _hip.check(lib.air_lfcc_fwd_padded_ex(*pcm_pointers(src),
-                                              _hip.ci(B), _hip.ci(L), _hip.dptr(out),
-                                              _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
-                                              _hip.dptr(self.plan(x.device), torch.uint8),
-                                              _hip.ci(self._flags()), _hip.ci(mode), _hip.dptr(sil, allow_none=True),
-                                              _hip.stream()),
-                   "air_lfcc_fwd_padded_ex")
-        return out
 
-    def forward_ragged(self, x, lengths, feat_len=750, start=None, padding="repeat"):
-        """A batch of utterances of DIFFERENT lengths in one launch: ``x`` (B, Lcap) float32 or int16 on the GPU, row b
-        holding ``lengths[b]`` samples (what follows them is never read) -> (B, out_dim, feat_len), row b being what
-        ``forward_padded`` gives for that utterance alone.  Does not mutate ``x``.  ``lengths``: int32 (B,); a GPU tensor is
-        used as is (the kernel clamps it to [1, Lcap]), a host tensor or list is checked (ValueError) and uploaded.
-        ``start`` / ``padding``: as in ``forward_padded``, each row's offset clamped to its own [0, T_b - feat_len]."""
-        self._check(x)
-        mode = pad_mode_id(padding)
-        B, Lcap = x.shape
-        lengths = device_lengths(lengths, B, Lcap, x.device)
-        if start is not None and not (torch.is_tensor(start) and start.is_cuda):
-            start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
-        src = _pcm_source(x)
-        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
-        sil = self.silence_row(x.device) if mode == 2 else None
-        lib = _hip.lib()
-        _hip.check(lib.air_lfcc_fwd_ragged(*pcm_pointers(src),
-                                           _hip.ci(B), _hip.ci(Lcap), _hip.dptr(lengths, torch.int32), _hip.dptr(out),
-                                           _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
-                                           _hip.dptr(self.plan(x.device), torch.uint8),
-                                           _hip.ci(self._flags()), _hip.ci(mode), _hip.dptr(sil, allow_none=True),
-                                           _hip.stream()),
-                   "air_lfcc_fwd_ragged")
-        return out
-
-    def _forward_i16(self, x, feat_len, start):
-        """16-bit PCM straight from the wav/flac samples (x = s / 32768 inside the kernel: the floats
-        soundfile / librosa hand the reference), in either layout (feat_len 0 = (B, T, D))."""
-        B, L = x.shape
-        x = x.contiguous()
-        T = 1 + L // self.fs
-        shape = (B, self.out_dim, feat_len) if feat_len > 0 else (B, T, self.out_dim)
-        out = torch.empty(shape, device=x.device, dtype=torch.float32)
-        lib = _hip.lib()
-        _hip.check(lib.air_lfcc_fwd_padded_i16(_hip.dptr(x, torch.int16), _hip.ci(B), _hip.ci(L), _hip.dptr(out),
-                                               _hip.ci(feat_len), _hip.dptr(start, torch.int32, True),
-                                               _hip.dptr(self.plan(x.device), torch.uint8),
-                                               _hip.ci(self._flags()), _hip.stream()),
-                   "air_lfcc_fwd_padded_i16")
-        return out
-
-    def _preemph_inplace(self, x):
-        preemph_inplace_(x)
-
-
-def preemph_inplace_(x):
-    """x[:, 1:] -= 0.97 * x[:, :-1] on the original samples, in place (feature_extraction.py:106, :157)."""
-    lib = _hip.lib()
-    B, L = x.shape
-    nbytes = lib.air_preemph_ws_bytes(_hip.ci(B), _hip.ci(L))
-    ws = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
-    _hip.check(lib.air_preemph_inplace(_hip.dptr(x), _hip.ci(B), _hip.ci(L), _hip.cf(0.97),
-                                       _hip.dptr(ws), _hip.csz(nbytes), _hip.stream()),
-               "air_preemph_inplace")
-
-
-class _Spectral(nn.Module):
-    """What the two spectrogram front-ends share (csrc/spectral.hip, ``air_spec_*``): the plan blob, the checks of
-    ``LFCC`` and its three entry points.  ``KIND`` / ``out_dim`` / ``fs`` (the hop) / ``NAME`` come from the subclass."""
-    KIND, NAME = 0, "?"
-
-    def __init__(self):
-        super().__init__()
-        self._plan = None
-        self._plan_key = None
+class _Spectral(_FrontEnd):
+    """The two spectrogram front-ends (csrc/spectral.hip, ``air_spec_*``).  ``KIND`` / ``out_dim`` / ``fs`` (the hop) /
+    ``NAME`` come from the subclass."""
+    KIND = 0
 
     def _flags(self):
         return 0
 
-    def plan(self, device):
-        """Device-resident plan blob (window, twiddles, banded mel filterbank)."""
-        key = str(device)
-        if self._plan is None or self._plan_key != key:
-            L = _hip.lib()
-            host = torch.zeros(L.air_spec_plan_bytes(), dtype=torch.uint8)
-            _hip.check(L.air_spec_plan_build(_hip.ci(self.KIND), _hip.hptr(host, torch.uint8)), "air_spec_plan_build")
-            self._plan = host.to(device)
-            self._plan_key = key
-        return self._plan
+    def _plan_build(self, lib):
+        host = torch.zeros(lib.air_spec_plan_bytes(), dtype=torch.uint8)
+        _hip.check(lib.air_spec_plan_build(_hip.ci(self.KIND), _hip.hptr(host, torch.uint8)), "air_spec_plan_build")
+        return host
 
-    def _check(self, x, padding=None):
-        if padding is not None and pad_mode_id(padding) == 2:
+    def _check(self, x, padding="repeat"):
+        mode = pad_mode_id(padding)
+        if mode == 2:
             raise NotImplementedError("padding='silence' prepends an LFCC frame (dataset.py:13-16) and is served by LFCC "
                                       "only; %s pads with 'repeat' or 'zero'" % self.NAME)
-        if x.dim() != 2:
-            raise ValueError("%s expects (batch, length), got %s" % (self.NAME, tuple(x.shape)))
-        if not x.is_cuda:
-            raise _hip.AirError("%s HIP path needs a GPU tensor; there is no CPU fallback" % self.NAME)
+        self._check_x(x)
+        return mode
 
-    def _check_lengths(self, host, Lcap):
-        """Host-side lengths beyond the [1, Lcap] check of ``ragged.device_lengths``."""
+    def _call_dense(self, lib, src, B, L, out, plan, flags):
+        _hip.check(lib.air_spec_fwd(_hip.ci(self.KIND), *pcm_pointers(src), B, L, out, plan, flags, _hip.stream()),
+                   "air_spec_fwd")
 
-    def _dense(self, x):
-        """(B, L) float32 or int16 on the GPU -> (B, T, out_dim).  Does not mutate ``x``."""
-        self._check(x)
-        B, L = x.shape
-        self._check_lengths(torch.tensor([L]), L)
-        src = _pcm_source(x)
-        out = torch.empty((B, 1 + L // self.fs, self.out_dim), device=x.device, dtype=torch.float32)
-        _hip.check(_hip.lib().air_spec_fwd(_hip.ci(self.KIND), *pcm_pointers(src), _hip.ci(B), _hip.ci(L),
-                                           _hip.dptr(out), _hip.dptr(self.plan(x.device), torch.uint8),
-                                           _hip.ci(self._flags()), _hip.stream()), "air_spec_fwd")
-        return out, src
-
-    def _padded(self, x, lengths, feat_len, start, padding):
-        mode = pad_mode_id(padding)
-        B, Lcap = x.shape
-        if start is not None and not (torch.is_tensor(start) and start.is_cuda):
-            start = torch.as_tensor(start, dtype=torch.int32).to(x.device)
-        src = _pcm_source(x)
-        out = torch.empty((B, self.out_dim, feat_len), device=x.device, dtype=torch.float32)
-        _hip.check(_hip.lib().air_spec_fwd_ragged(_hip.ci(self.KIND), *pcm_pointers(src), _hip.ci(B), _hip.ci(Lcap),
-                                                  _hip.dptr(lengths, torch.int32, True), _hip.dptr(out), _hip.ci(feat_len),
-                                                  _hip.dptr(start, torch.int32, True),
-                                                  _hip.dptr(self.plan(x.device), torch.uint8), _hip.ci(self._flags()),
-                                                  _hip.ci(mode), _hip.stream()), "air_spec_fwd_ragged")
-        return out
-
-    def forward_padded(self, x, feat_len=750, start=None, padding="repeat"):
-        """Fused front-end -> pad / chop -> transpose: (B, L) -> (B, out_dim, feat_len), what dataset.py:62-79 +
-        main_train.py:338 build on the host.  Does not mutate ``x``.  ``start`` / ``padding``: as in
-        ``LFCC.forward_padded``, without 'silence' (NotImplementedError)."""
-        self._check(x, padding)
-        self._check_lengths(torch.tensor([x.shape[1]]), x.shape[1])
-        return self._padded(x, None, feat_len, start, padding)
-
-    def forward_ragged(self, x, lengths, feat_len=750, start=None, padding="repeat"):
-        """Utterances of different lengths in one launch: row b of ``x`` (B, Lcap) holds ``lengths[b]`` samples ->
-        (B, out_dim, feat_len), row b being what ``forward_padded`` gives for that utterance alone.  ``lengths``: as in
-        ``LFCC.forward_ragged`` - a GPU tensor is used as is (the kernel clamps it to [1, Lcap]), a host tensor or list
-        is checked (ValueError) and uploaded."""
-        self._check(x, padding)
-        B, Lcap = x.shape
-        lengths = device_lengths(lengths, B, Lcap, x.device, extra_check=self._check_lengths)
-        return self._padded(x, lengths, feat_len, start, padding)
+    def _call_padded(self, lib, rows, lengths, tail, mode, device):
+        _hip.check(lib.air_spec_fwd_ragged(_hip.ci(self.KIND), *rows, _hip.dptr(lengths, torch.int32, True), *tail,
+                                           _hip.stream()), "air_spec_fwd_ragged")
 
 
 class STFT(_Spectral):
@@ -355,11 +322,9 @@ class STFT(_Spectral):
         return 1 if self.with_emphasis else 0
 
     def forward(self, x):
+        self._check(x)
         out, src = self._dense(x)
-        if self.with_emphasis and self.mutate_input and x.dtype != torch.int16:  # (integers: nothing to mutate)
-            preemph_inplace_(src)
-            if src is not x:
-                x.copy_(src)
+        self._emphasise(x, src)
         return out
 
 
@@ -390,6 +355,7 @@ class Melspec(_Spectral):
 
     def forward_frames(self, x):
         """(B, L) -> (B, T, 128): the frame-major layout of ``LFCC.forward`` / ``STFT.forward``."""
+        self._check(x)
         return self._dense(x)[0]
 
     def forward_batch(self, x):

@@ -380,3 +380,28 @@ def test_trainer_replays_and_scores_on_stft_features():
         runs.append((losses, tr.model.arena().flat.clone()))
     assert all(np.isfinite(runs[0][0])) and runs[0][0] == runs[1][0] and torch.equal(runs[0][1], runs[1][1])
     assert tr.score(pcm).shape == (2,)
+
+
+# ---------------------------------------------------------------------------- one spectrum for LFCC and STFT
+@pytest.mark.parametrize("emph", [True, False])
+def test_lfcc_is_filterbank_log_dct_of_the_stft_kernels_spectrum(emph):
+    """LFCC and STFT run the same pipeline up to the power spectrum (csrc/air_spec512.h): the static cepstra of the LFCC
+    kernel are DCT(log10(P @ lfcc_fb + eps)) of the power P the STFT kernel writes for the same input, taken on the host in
+    fp64 with the module's own ``lfcc_fb`` and ``l_dct.weight``.  Shapes: the tile edges of the two kernels (28 written
+    frames per LFCC tile, 32 per STFT tile); white noise of amplitude 0.1, so that no filter sums near zero.  Tolerance:
+    the one ``test_lfcc_gpu.py::test_lfcc_vs_oracle_shapes`` holds LFCC to against its oracle."""
+    from asvspoof2021_air_amd.feature_extraction import LFCC, STFT
+    tol = 3e-5
+    lfcc = LFCC(320, 160, 512, 16000, 20, with_emphasis=emph, with_delta=False).cuda()
+    stft = STFT(320, 160, 512, 16000, with_emphasis=emph).cuda()
+    lfcc.mutate_input = stft.mutate_input = False
+    fb, dct = lfcc.lfcc_fb.double().cpu(), lfcc.l_dct.weight.double().cpu()
+    for L in (159, 28 * 160 - 1, 28 * 160, 32 * 160 - 1, 32 * 160, 64 * 160 + 1):
+        x = (0.1 * torch.randn(2, L, generator=torch.Generator().manual_seed(900 + L))).cuda()
+        got = lfcc(x)
+        power = stft(x).double().cpu()
+        want = torch.log10(power @ fb + torch.finfo(torch.float32).eps) @ dct.t()
+        assert got.shape == want.shape == (2, 1 + L // 160, 20)
+        err = float((got.double().cpu() - want).abs().max())
+        print("emphasis %s, (2, %d): LFCC vs DCT(log10(STFT @ fb + eps)) %.3g (bound %.3g)" % (emph, L, err, tol))
+        assert err <= tol, (emph, L, err)

@@ -4,7 +4,7 @@
 
 B = 64 rows of 64 000 samples (4 s), fp32.  Per kind: the dense call, (B, T, D) with T = 401 (STFT) / 501 (Melspec), and
 the padded call, those frames repeat-padded into (B, D, 750).  Beside them the LFCC padded call at the same shape
-(csrc/lfcc.hip, untouched by this change) and each launch's write floor: its output bytes over the 6.29 TB/s a float4 copy
+(csrc/lfcc.hip) and each launch's write floor: its output bytes over the 6.29 TB/s a float4 copy
 reaches on an MI355X (MI355X_MICROARCH.md).  These are CALL times: device events around ``reps`` back-to-back module
 calls (each allocates its output from the caching allocator and launches one kernel), windows of 20 - 30 ms; the
 variants alternate round by round, the first two rounds only warm up; median and min .. max of the rest.  Kernel times:

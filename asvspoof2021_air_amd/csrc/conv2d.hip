@@ -118,23 +118,6 @@ __global__ void pack_weights_batch_kernel(const PackJobs jb) {
                     (int)blockIdx.x - jb.blk0[j], jb.blk0[j + 1] - jb.blk0[j]);
 }
 
-// zero-upsample dy (B,C,Ho,Wo) -> (B,C,Hu,Wu) with u[2i][2j] = dy[i][j]
-__global__ void upsample2_kernel(const float* __restrict__ dy, float* __restrict__ up, int Ho,
-                                 int Wo, int Hu, int Wu, size_t planes) {
-  const size_t total = planes * Hu * Wu;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (size_t)gridDim.x * blockDim.x) {
-    const int wu = (int)(e % Wu);
-    const size_t r = e / Wu;
-    const int hu = (int)(r % Hu);
-    const size_t pl = r / Hu;
-    float v = 0.0f;
-    if (!(wu & 1) && !(hu & 1) && (hu >> 1) < Ho && (wu >> 1) < Wo)
-      v = dy[(pl * Ho + (hu >> 1)) * Wo + (wu >> 1)];
-    up[e] = v;
-  }
-}
-
 struct FwdArgs {
   const float* x;      // (B, Cin, H, W)
   const float* wp;     // packed weights
@@ -1339,6 +1322,14 @@ int pack_run_jobs(hipStream_t st) {
   return AIR_OK;
 }
 
+// n source taps first, first + step, ...: (n, 0, 1) all taps in order, (n, n - 1, -1) flipped
+TapSel tap_run(int n, int first, int step) {
+  TapSel sel;
+  sel.n = n;
+  for (int t = 0; t < n; ++t) sel.idx[t] = first + step * t;
+  return sel;
+}
+
 int pack(const float* w, float*& wp, int Cout, int Cin, int taps_full, int transpose, int ck,
          int mt, const TapSel& sel, hipStream_t st) {
   const int M = transpose ? Cin : Cout, Kc = transpose ? Cout : Cin;
@@ -1374,20 +1365,28 @@ double conv_flops(const AirConv2d* p) {
 }
 
 // stride-2 3x3 wgrad holds a 65-column patch per channel: use 32-channel tiles there
-int wgrad_ct(const AirConv2d* p) { return (p->sh == 2 && p->Cout % 128 == 0) ? 32 : 64; }
+struct WgradGeom {
+  int B, Cin, H, W, Cout, KH, KW, S, ph, pw, Ho, Wo;
+  int dil;
+  size_t x_bstride, dy_bstride;
+};
+WgradGeom wgrad_geom(const AirConv2d* p) {
+  return {p->B, p->Cin, p->H, p->W, p->Cout, p->KH, p->KW, p->sh, p->ph, p->pw, p->Ho, p->Wo,
+          1, (size_t)p->Cin * p->H * p->W, (size_t)p->Cout * p->Ho * p->Wo};
+}
+int wgrad_ct(const WgradGeom& g) { return (g.S == 2 && g.Cout % 128 == 0) ? 32 : 64; }
 
 // workgroups of the split-K direct weight gradient: one per CU, two for the 1x1 stride-2 layers (16 MFMAs between
 // the barriers of a tile and 50 KB of LDS: a second resident workgroup covers the waits, 240 -> 212 us over the
 // ResNet's three shortcuts)
 int wgrad_wgs(int KH, int KW, int S) { return air_opt(AIR_OPT_WGRAD_WGS) * ((KH == 1 && KW == 1 && S == 2) ? 2 : 1); }
 
-int wgrad_nsplit(const AirConv2d* p) {
-  const int WT = (p->Wo + PXT - 1) / PXT;
-  const int ntiles = p->B * p->Ho * WT;
-  const int ct = wgrad_ct(p);
-  const int ncot = p->Cout / (ct == 32 ? 128 : 64), ncit = (p->Cin + ct - 1) / ct;
-  const int total = wgrad_wgs(p->KH, p->KW, p->sh);
-  int target = total / (ncot * ncit);  // workgroups in flight over the whole chip
+// pixel-tile splits (= partials) of the split-K direct weight gradient (the dilated 1 x 3 conv1d layers: WGRAD_WGS as it is)
+int wgrad_nsplit(const WgradGeom& g) {
+  const int ntiles = g.B * g.Ho * ((g.Wo + PXT - 1) / PXT);
+  const int ct = wgrad_ct(g);
+  const int ncot = g.Cout / (ct == 32 ? 128 : 64), ncit = (g.Cin + ct - 1) / ct;
+  int target = wgrad_wgs(g.KH, g.KW, g.S) / (ncot * ncit);  // workgroups in flight over the whole chip
   if (target < 1) target = 1;
   if (target > ntiles) target = ntiles;
   return target;
@@ -1629,36 +1628,40 @@ __global__ __launch_bounds__(256) void conv_wgrad_3x3_skinny_kernel(const Skinny
   }
 }
 
-struct WgradGeom {
-  int B, Cin, H, W, Cout, KH, KW, S, ph, pw, Ho, Wo;
-  int dil;
-  size_t x_bstride, dy_bstride;
-};
+// The tail every weight-gradient route shares: `launch(partial)` writes `parts` partial gradients of `wsz` floats into the
+// workspace, reduce_partials_kernel sums them in order into dw (taps: the partials' layout, see the kernel).
+template <class Launch>
+int wgrad_parts(void* ws, size_t ws_bytes, int parts, size_t wsz, int taps, float* dw, hipStream_t st, Launch launch) {
+  if (!ws || ws_bytes < (size_t)parts * wsz * sizeof(float)) return AIR_EWORKSPACE;
+  float* partial = reinterpret_cast<float*>(ws);
+  const int rc = launch(partial);
+  if (rc != AIR_OK) return rc;
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, parts)), dim3(256), 0, st, partial, dw, wsz, parts, taps);
+  AIR_CHECK_LAUNCH();
+  return AIR_OK;
+}
 
 int run_wgrad(const WgradGeom& g, const float* x, const float* dy, float* dw, const float* in_scale,
               const float* in_shift, int relu, void* ws, size_t ws_bytes, double flops,
               hipStream_t st) {
   const size_t wsz = (size_t)g.Cout * g.Cin * g.KH * g.KW;
   WgradArgs a;
-  a.x = x; a.dy = dy; a.partial = reinterpret_cast<float*>(ws);
+  a.x = x; a.dy = dy;
   a.scale = in_scale; a.shift = in_shift;
   a.B = g.B; a.Cin = g.Cin; a.H = g.H; a.W = g.W; a.Cout = g.Cout; a.Ho = g.Ho; a.Wo = g.Wo;
   a.ph = g.ph; a.pw = g.pw; a.relu = relu;
   a.x_bstride = g.x_bstride; a.dy_bstride = g.dy_bstride;
   a.WT = (g.Wo + PXT - 1) / PXT;
   a.ntiles = g.B * g.Ho * a.WT;
-  const int ct = (g.S == 2 && g.Cout % 128 == 0) ? 32 : 64;
+  const int ct = wgrad_ct(g);
   a.ncot = g.Cout / (ct == 32 ? 128 : 64);
   a.ncit = (g.Cin + ct - 1) / ct;
-  const int total = g.dil == 1 ? wgrad_wgs(g.KH, g.KW, g.S) : air_opt(AIR_OPT_WGRAD_WGS);
-  int nsplit = total / (a.ncot * a.ncit);  // workgroups in flight over the whole chip
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > a.ntiles) nsplit = a.ntiles;
-  a.nsplit = nsplit;
+  a.nsplit = wgrad_nsplit(g);
   a.tiles_per_split = (a.ntiles + a.nsplit - 1) / a.nsplit;
-  if (!ws || ws_bytes < (size_t)a.nsplit * wsz * sizeof(float)) return AIR_EWORKSPACE;
   const int nblk = a.ncot * a.ncit * a.nsplit;
   const int key = g.KH * 1000 + g.KW * 100 + g.S * 10 + (g.dil - 1);
+  return wgrad_parts(ws, ws_bytes, a.nsplit, wsz, g.KH * g.KW, dw, st, [&](float* partial) -> int {
+    a.partial = partial;
 #define AIR_WG_CASE(KH_, KW_, S_, CT_, DIL_, KID_)                                              \
   if (key == KH_ * 1000 + KW_ * 100 + S_ * 10 + (DIL_ - 1) && ct == CT_) {                       \
     AirProfScope ps(KID_, flops, st);                                                            \
@@ -1669,21 +1672,19 @@ int run_wgrad(const WgradGeom& g, const float* x, const float* dy, float* dw, co
       hipLaunchKernelGGL((conv_wgrad_kernel<KH_, KW_, S_, CT_, 0, DIL_>), dim3(nblk), dim3(256), \
                          0, st, a);                                                              \
     AIR_CHECK_LAUNCH();                                                                          \
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, a.nsplit)), dim3(256), 0, st, \
-                       reinterpret_cast<const float*>(ws), dw, wsz, a.nsplit, g.KH * g.KW);      \
-    AIR_CHECK_LAUNCH();                                                                          \
     return AIR_OK;                                                                               \
   }
-  AIR_WG_CASE(3, 3, 1, 64, 1, AIR_K_CONV_WG_331)
-  AIR_WG_CASE(3, 3, 2, 32, 1, AIR_K_CONV_WG_332)
-  AIR_WG_CASE(1, 1, 1, 64, 1, AIR_K_CONV_WG_111)
-  AIR_WG_CASE(1, 1, 2, 32, 1, AIR_K_CONV_WG_112)
-  AIR_WG_CASE(1, 5, 1, 64, 1, AIR_K_CONV_WG_1D)
-  AIR_WG_CASE(1, 3, 1, 64, 2, AIR_K_CONV_WG_1D)
-  AIR_WG_CASE(1, 3, 1, 64, 3, AIR_K_CONV_WG_1D)
-  AIR_WG_CASE(1, 3, 1, 64, 4, AIR_K_CONV_WG_1D)
+    AIR_WG_CASE(3, 3, 1, 64, 1, AIR_K_CONV_WG_331)
+    AIR_WG_CASE(3, 3, 2, 32, 1, AIR_K_CONV_WG_332)
+    AIR_WG_CASE(1, 1, 1, 64, 1, AIR_K_CONV_WG_111)
+    AIR_WG_CASE(1, 1, 2, 32, 1, AIR_K_CONV_WG_112)
+    AIR_WG_CASE(1, 5, 1, 64, 1, AIR_K_CONV_WG_1D)
+    AIR_WG_CASE(1, 3, 1, 64, 2, AIR_K_CONV_WG_1D)
+    AIR_WG_CASE(1, 3, 1, 64, 3, AIR_K_CONV_WG_1D)
+    AIR_WG_CASE(1, 3, 1, 64, 4, AIR_K_CONV_WG_1D)
 #undef AIR_WG_CASE
-  return AIR_EUNSUPPORTED;
+    return AIR_EUNSUPPORTED;
+  });
 }
 
 }  // namespace
@@ -1710,8 +1711,7 @@ static int skinny_wgrad_chunks(const AirConv2d* p) {
   return n;
 }
 static bool skinny3_wgrad_ok(const AirConv2d* p) {
-  return p->KH == 3 && p->KW == 3 && p->sh == 1 && p->sw == 1 && p->ph == 1 && p->pw == 1 && p->Cout == 64 &&
-         p->Cin == 16 && p->W >= 4 && air_opt(AIR_OPT_SKINNY_WGRAD);
+  return wino_shape(p) && p->Cout == 64 && p->Cin == 16 && p->W >= 4 && air_opt(AIR_OPT_SKINNY_WGRAD);
 }
 static int skinny3_wgrad_parts(const AirConv2d* p) {
   const int units = p->B * p->H;  // one workgroup (4 waves, a row's quarters each) per row, at most one per CU
@@ -1722,76 +1722,16 @@ static int skinny_wgrad_chunk_px(const AirConv2d* p, int nchunk) {
   return ((hw + nchunk - 1) / nchunk + 63) / 64 * 64;
 }
 
-// the split-bf16 forward of a 3x3 / stride 2 / pad 1 layer (conv_bf3.hip; option CONV_S2 bit 4)
+// 3x3 / stride 2 / pad 1: the shape of the split-bf16 kernels (conv_bf3.hip) and of the one-pass data gradient
+static bool s2_shape(const AirConv2d* p) {
+  return p->KH == 3 && p->KW == 3 && p->sh == 2 && p->sw == 2 && p->ph == 1 && p->pw == 1;
+}
+// the split-bf16 forward (option CONV_S2 bit 4) and weight gradient (bit 16); generic_ok: no direct_ok layer among them
 static bool bf3_fwd_ok(const AirConv2d* p) {
-  return p->KH == 3 && p->KW == 3 && p->sh == 2 && p->sw == 2 && p->ph == 1 && p->pw == 1 && generic_ok(p) && !direct_ok(p) &&
-         air_bf3_s2_ok(p->B, p->Cin, p->H, p->W, p->Cout);
+  return s2_shape(p) && generic_ok(p) && air_bf3_s2_ok(p->B, p->Cin, p->H, p->W, p->Cout);
 }
-
 static bool bf3_wgrad_ok(const AirConv2d* p) {
-  return p->KH == 3 && p->KW == 3 && p->sh == 2 && p->sw == 2 && p->ph == 1 && p->pw == 1 && generic_ok(p) && !direct_ok(p) &&
-         air_bf3_s2w_ok(p->B, p->Cin, p->H, p->W, p->Cout);
-}
-
-size_t air_conv2d_ws_bytes(const AirConv2d* p) {
-  if (!p || !shape_ok(p)) return 0;
-  const size_t wsz = (size_t)p->Cout * p->Cin * p->KH * p->KW;
-  if (direct_ok(p)) return (size_t)p->B * p->Ho * wsz * sizeof(float) + 256;
-  if (!generic_ok(p)) return 0;
-  size_t fwd = wsz;
-  {  // K-split forward: the weight slab and up to four partial copies of y behind it (fwd_generic)
-    const size_t slab = (size_t)((p->Cout + 63) / 64 * 64) * ((p->Cin + 31) / 32 * 32) * p->KH * p->KW + 64;
-    const int ntiles = p->B * p->Ho * ((p->Wo + PXT - 1) / PXT);
-    if (((ntiles + NWAVE - 1) / NWAVE) * ((p->Cout + 31) / 32) <= 1536)
-      fwd = slab + 4 * (size_t)p->B * p->Cout * p->Ho * p->Wo;
-  }
-  if (bf3_fwd_ok(p)) {  // bf16 planes: 6 bytes per weight
-    const size_t pl = (air_bf3_s2_packed_bytes(p->Cout, p->Cin, true) + 3) / 4;
-    if (pl > fwd) fwd = pl;
-  }
-  size_t dgrad = packed_dgrad_elems(p);
-  if (wino_shape(p)) {  // transformed weights are 16/9 the size
-    const size_t wf = air_wino_packed_elems(p->Cout, p->Cin), wd = air_wino_packed_elems(p->Cin, p->Cout);
-    if (wf > fwd) fwd = wf;
-    if (wd > dgrad) dgrad = wd;
-    const size_t wf4 = air_wino4_packed_elems(p->Cout, p->Cin), wd4 = air_wino4_packed_elems(p->Cin, p->Cout);
-    if (wf4 > fwd) fwd = wf4;  // F(4x4,3x3): 36/9 the size
-    if (wd4 > dgrad) dgrad = wd4;
-  }
-  size_t wgrad = (size_t)wgrad_nsplit(p) * wsz;
-  if (wino_shape(p) && air_wino_wgrad_ok(p->B, p->Cin, p->H, p->W, p->Cout)) {
-    const size_t ww = (size_t)air_wino_wgrad_nsplit(p->B, p->Cin, p->H, p->W, p->Cout) * wsz;
-    if (ww > wgrad) wgrad = ww;
-  }
-  if (wino_pad_wgrad(p)) {  // zero-padded copy of x (64 channels) + partials + 64-channel dW
-    const size_t pad = (size_t)p->B * 64 * p->H * p->W + 64 +
-                       (size_t)(air_wino_wgrad_nsplit(p->B, 64, p->H, p->W, p->Cout) + 1) * p->Cout * 64 * 9;
-    if (pad > wgrad) wgrad = pad;
-  }
-  if (const int nch = skinny_wgrad_chunks(p)) {
-    const size_t sk = (size_t)p->B * nch * wsz;
-    if (sk > wgrad) wgrad = sk;
-  }
-  if (bf3_wgrad_ok(p)) {
-    const size_t sk = (size_t)air_bf3_s2w_nseg(p->B, p->Cin, p->Ho, p->Wo, p->Cout) * wsz;
-    if (sk > wgrad) wgrad = sk;
-  }
-  if (skinny3_wgrad_ok(p)) {
-    const size_t sk = (size_t)skinny3_wgrad_parts(p) * wsz;
-    if (sk > wgrad) wgrad = sk;
-  }
-  size_t m = fwd > dgrad ? fwd : dgrad;
-  if (wgrad > m) m = wgrad;
-  return m * sizeof(float) + 256;
-}
-
-// which Winograd kernel takes this 3x3 / stride 1 / pad 1 layer for `pass` (0 forward, 1 dgrad): 4, 2 or 0 (none)
-static int wino_kind(const AirConv2d* p, int pass) {
-  if (!wino_shape(p) || !generic_ok(p)) return 0;
-  const int M = pass ? p->Cin : p->Cout, Kc = pass ? p->Cout : p->Cin;
-  if (air_wino4_ok(p->B, Kc, p->H, p->W, M)) return 4;
-  if (air_wino_ok(p->B, Kc, p->H, p->W, M)) return 2;
-  return 0;
+  return s2_shape(p) && generic_ok(p) && air_bf3_s2w_ok(p->B, p->Cin, p->H, p->W, p->Cout);
 }
 
 // floats of the forward weight slab (channel tiles and K chunks zero-padded), rounded up to 64
@@ -1814,28 +1754,28 @@ static int fwd_ksplit(const AirConv2d* p, int ck, int mt) {
   return k < 1 ? 1 : k;
 }
 
-// forward on the direct kernels (whatever pack mode is current: see PackCtx)
-static int fwd_generic(const AirConv2d* p, const float* x, const float* w, float* y, const float* in_scale,
-                       const float* in_shift, int relu, const float* residual, float* wp, hipStream_t st,
-                       size_t ws_floats = 0) {
+// K-chunk channels and pixel tiles of the forward on the direct kernels
+static void fwd_tiling(const AirConv2d* p, int* ck_out, int* mt_out) {
   const int taps = p->KH * p->KW;
   // stride-2 3x3: the 65-column patches of 8 channels leave room for ONE workgroup per CU (88 KB of LDS);
   // 4-channel chunks fit three (option CONV_S2, bit 1)
   const bool s2ck4 = taps == 9 && p->sh == 2 && p->Cin % 4 == 0 && (air_opt(AIR_OPT_CONV_S2) & 1);
   // 1x1 stride 2 (the shortcuts): 32-channel chunks of 63-column rows are 80 KB - one workgroup per CU again; 16 fit three
   const bool s2ck16 = taps == 1 && p->sh == 2 && p->Cin % 16 == 0 && (air_opt(AIR_OPT_CONV_S2) & 1);
-  const int ck = s2ck4 ? 4 : (s2ck16 ? 16 : pick_ck(taps, p->Cin));
-  TapSel sel;
-  sel.n = taps;
-  for (int t = 0; t < taps; ++t) sel.idx[t] = t;
+  *ck_out = s2ck4 ? 4 : (s2ck16 ? 16 : pick_ck(taps, p->Cin));
   // (with 4-channel chunks the 64-channel tile measured faster on every ResNet shape, whatever the round count)
-  const int mt = s2ck4 && p->Cout > 32 && !air_opt(AIR_OPT_CONV_MT) ? 2 : mt_for(p->B, p->Ho, p->Wo, p->Cout);
+  *mt_out = s2ck4 && p->Cout > 32 && !air_opt(AIR_OPT_CONV_MT) ? 2 : mt_for(p->B, p->Ho, p->Wo, p->Cout);
+}
+
+// forward on the direct kernels (whatever pack mode is current: see PackCtx); ksplit: the route's partial count
+static int fwd_generic(const AirConv2d* p, const float* x, const float* w, float* y, const float* in_scale,
+                       const float* in_shift, int relu, const float* residual, float* wp, hipStream_t st, int ksplit) {
+  const int taps = p->KH * p->KW;
+  int ck, mt;
+  fwd_tiling(p, &ck, &mt);
   float* const ws0 = wp;  // (pack() points wp at the caller's slab under PK_USE)
-  int rc = pack(w, wp, p->Cout, p->Cin, taps, 0, ck, mt, sel, st);
+  int rc = pack(w, wp, p->Cout, p->Cin, taps, 0, ck, mt, tap_run(taps, 0, 1), st);
   if (rc != AIR_OK) return rc;
-  int ksplit = (in_scale == nullptr && residual == nullptr && !pk_dry()) ? fwd_ksplit(p, ck, mt) : 1;
-  // (a caller that sized its workspace by an older rule gets the unsplit loop)
-  if (ksplit > 1 && ws_floats < fwd_pack_elems(p, ck, mt) + (size_t)ksplit * p->B * p->Cout * p->Ho * p->Wo) ksplit = 1;
   return run_fwd(x, wp, y, in_scale, in_shift, relu, residual,
                  plain_geom(p->B, p->Cin, p->H, p->W, p->Cout, p->KH, p->KW, p->sh, p->ph, p->pw,
                             p->Ho, p->Wo),
@@ -1845,8 +1785,7 @@ static int fwd_generic(const AirConv2d* p, const float* x, const float* w, float
 // stride-2 3x3 data gradient in one pass (conv_s2_dgrad_kernel); option CONV_S2 bit 2, 0 = the four class launches
 constexpr int S2D_CK = 8;
 static bool s2d_ok(const AirConv2d* p) {
-  return p->KH == 3 && p->KW == 3 && p->sh == 2 && p->sw == 2 && p->ph == 1 && p->pw == 1 && p->Cout % S2D_CK == 0 &&
-         (air_opt(AIR_OPT_CONV_S2) & 2) != 0;
+  return s2_shape(p) && p->Cout % S2D_CK == 0 && (air_opt(AIR_OPT_CONV_S2) & 2) != 0;
 }
 static int s2d_mt(const AirConv2d* p) { return mt_for(p->B, p->Ho, p->Wo, p->Cin); }
 
@@ -1891,10 +1830,7 @@ static int dgrad_generic(const AirConv2d* p, const float* dy, const float* w, fl
     const int ck = pick_ck(3, p->Cout);
     const int mt = mt_for(p->B, 1, p->W, p->Cin);
     for (int h = 0; h < p->KH; ++h) {
-      TapSel sel;
-      sel.n = 3;
-      for (int j = 0; j < 3; ++j) sel.idx[j] = h * 3 + (2 - j);  // flipped along w
-      int rc = pack(w, wp, p->Cout, p->Cin, taps, 1, ck, mt, sel, st);
+      int rc = pack(w, wp, p->Cout, p->Cin, taps, 1, ck, mt, tap_run(3, h * 3 + 2, -1), st);  // flipped along w
       if (rc != AIR_OK) return rc;
       FwdGeom g = plain_geom(p->B, p->Cout, 1, p->Wo, p->Cin, 1, 3, 1, 0, 2 - p->pw, 1, p->W);
       g.oh_mul = 1; g.ow_row = p->W; g.ow_mul = 1; g.o_off = h * p->W; g.oplane = plane;
@@ -1907,11 +1843,8 @@ static int dgrad_generic(const AirConv2d* p, const float* dy, const float* w, fl
   if (p->sh == 1) {
     // stride 1: dx = conv(dy, flipped taps) with padding K-1-p
     const int ck = pick_ck(taps, p->Cout);
-    TapSel sel;
-    sel.n = taps;
-    for (int t = 0; t < taps; ++t) sel.idx[t] = taps - 1 - t;
     const int mt = mt_for(p->B, p->H, p->W, p->Cin);
-    int rc = pack(w, wp, p->Cout, p->Cin, taps, 1, ck, mt, sel, st);
+    int rc = pack(w, wp, p->Cout, p->Cin, taps, 1, ck, mt, tap_run(taps, taps - 1, -1), st);
     if (rc != AIR_OK) return rc;
     return run_fwd(dy, wp, dx, nullptr, nullptr, 0, accumulate,
                    plain_geom(p->B, p->Cout, p->Ho, p->Wo, p->Cin, p->KH, p->KW, 1,
@@ -1937,11 +1870,8 @@ static int dgrad_generic(const AirConv2d* p, const float* dy, const float* w, fl
         return AIR_ELAUNCH;
     }
     const int ck = pick_ck(1, p->Cout);
-    TapSel sel;
-    sel.n = 1;
-    sel.idx[0] = 0;
     const int mt = mt_for(p->B, p->Ho, p->Wo, p->Cin);
-    int rc = pack(w, wp, p->Cout, p->Cin, 1, 1, ck, mt, sel, st);
+    int rc = pack(w, wp, p->Cout, p->Cin, 1, 1, ck, mt, tap_run(1, 0, 1), st);
     if (rc != AIR_OK) return rc;
     FwdGeom g = plain_geom(p->B, p->Cout, p->Ho, p->Wo, p->Cin, 1, 1, 1, 0, 0, p->Ho, p->Wo);
     g.oh_mul = 2; g.ow_row = p->W; g.ow_mul = 2; g.o_off = 0; g.oplane = plane;
@@ -1949,11 +1879,8 @@ static int dgrad_generic(const AirConv2d* p, const float* dy, const float* w, fl
     return run_fwd(dy, wp, dx, nullptr, nullptr, 0, dx, g, ck, mt, conv_flops(p), st);
   }
   if (s2d_ok(p)) {
-    TapSel sel;
-    sel.n = 9;
-    for (int t = 0; t < 9; ++t) sel.idx[t] = t;
     const int mt = s2d_mt(p);
-    int rc = pack(w, wp, p->Cout, p->Cin, 9, 1, S2D_CK, mt, sel, st);
+    int rc = pack(w, wp, p->Cout, p->Cin, 9, 1, S2D_CK, mt, tap_run(9, 0, 1), st);
     if (rc != AIR_OK) return rc;
     return run_s2d(p, dy, nullptr, wp, nullptr, dx, accumulate, mt, st);
   }
@@ -1984,60 +1911,165 @@ static int dgrad_generic(const AirConv2d* p, const float* dy, const float* w, fl
   return AIR_OK;
 }
 
-// (direct_ok: the ResNet's 1 -> 16 first layer reads its weights as they are)
-static bool generic_pack_ok(const AirConv2d* p, int pass) {
-  return generic_ok(p) && !direct_ok(p) && wino_kind(p, pass) == 0;
+// ---- routes: which kernel serves one pass of a layer under the current dispatch options, and what the call needs.
+// Every entry point below validates its pointers, takes the pass's route and switches on its kind; the size and layout
+// queries return fields of it.  Host arithmetic over p, the flags and air_opt only: nothing is launched or allocated.
+// RT_NONE: no kernel (AIR_EUNSUPPORTED).  RT_DIRECT: the small-Cout kernels, weights as they are.  RT_WINO4 / RT_WINO2:
+// Winograd F(4x4 | 3x4, 3x3) / F(2x2, 3x3).  RT_BF3: split-bf16 stride 2.  RT_SLABS: the f32 MFMA kernels on pack()'s slabs.
+enum RouteKind { RT_NONE = 0, RT_DIRECT, RT_WINO4, RT_WINO2, RT_BF3, RT_SLABS,
+                 RT_WG_WINO, RT_WG_SKINNY3, RT_WG_WINO_PAD, RT_WG_SKINNY1, RT_WG_SPLITK };  // weight gradients only
+struct Route {
+  int kind;
+  int layout;         // AIR_PACK_* of the packed weights
+  size_t pack_bytes;  // what air_conv2d_prepack writes (0: the pass has no packed form)
+  size_t ws_floats;   // the workspace the call checks for
+  int parts;          // partial results that reduce_partials_kernel sums (<= 1: none)
+  int taps;           //   and its tap argument
+  size_t bn_bytes;    // fused BatchNorm records of the epilogue (0: none)
+};
+
+// 3x3 / stride 1 / pad 1 forward (pass 0) or data gradient (pass 1: the channels swap roles) on a Winograd kernel
+static bool wino_route(const AirConv2d* p, int pass, Route* r) {
+  if (!wino_shape(p)) return false;
+  const int M = pass ? p->Cin : p->Cout, Kc = pass ? p->Cout : p->Cin;
+  if (air_wino4_ok(p->B, Kc, p->H, p->W, M)) {  // transformed weights: 36/9 the size
+    *r = {RT_WINO4, AIR_PACK_WINO4, 0, air_wino4_packed_elems(M, Kc), 0, 0, 0};
+    if (M % 32 == 0) r->bn_bytes = air_wino4_stats_bytes(p->B, p->H, p->W, M);  // (whole 32-channel slabs)
+  } else if (air_wino_ok(p->B, Kc, p->H, p->W, M)) {  // 16/9 the size
+    *r = {RT_WINO2, AIR_PACK_WINO2, 0, air_wino_packed_elems(M, Kc), 0, 0, 0};
+  } else {
+    return false;
+  }
+  r->pack_bytes = r->ws_floats * sizeof(float);
+  return true;
 }
 
-size_t air_conv2d_prepack_bytes(const AirConv2d* p, int pass) {
-  if (!p || !shape_ok(p)) return 0;
-  const int kind = wino_kind(p, pass);
-  const int M = pass ? p->Cin : p->Cout, Kc = pass ? p->Cout : p->Cin;
-  if (kind == 4) return air_wino4_packed_elems(M, Kc) * sizeof(float);
-  if (kind == 2) return air_wino_packed_elems(M, Kc) * sizeof(float);
-  if (pass == 0 && bf3_fwd_ok(p)) return air_bf3_s2_packed_bytes(p->Cout, p->Cin, false);
-  if (!generic_pack_ok(p, pass)) return 0;
+// the PK_SIZE walk of fwd_generic / dgrad_generic: bytes of the slabs the pass consumes (false: it has no kernel)
+static bool slab_bytes(const AirConv2d* p, int pass, size_t* bytes) {
   PackScope size(PK_SIZE, nullptr);
   float* none = nullptr;
   const int rc = pass ? dgrad_generic(p, nullptr, nullptr, nullptr, nullptr, none, nullptr)
-                      : fwd_generic(p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, none, nullptr);
-  return rc == AIR_OK ? g_pk.used * sizeof(float) : 0;
+                      : fwd_generic(p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, none, nullptr, 1);
+  *bytes = g_pk.used * sizeof(float);
+  return rc == AIR_OK;
+}
+
+// pro: the fused BatchNorm-apply + ReLU prologue; res: a residual operand
+static Route fwd_route(const AirConv2d* p, bool pro, bool res) {
+  Route r = {};
+  if (direct_ok(p)) {  // (the ResNet's 1 -> 16 first layer: plain convolutions only)
+    if (!pro && !res) r.kind = RT_DIRECT;
+    return r;
+  }
+  if (!generic_ok(p) || (pro && p->Cin > MAXC)) return r;
+  if (!pro && wino_route(p, 0, &r)) return r;
+  if (!pro && !res && bf3_fwd_ok(p)) {  // bf16 planes: 6 bytes per weight
+    const size_t bytes = air_bf3_s2_packed_bytes(p->Cout, p->Cin, false);
+    return {RT_BF3, AIR_PACK_BF3, bytes, (bytes + 3) / 4, 0, 0, 0};
+  }
+  int ck, mt;
+  fwd_tiling(p, &ck, &mt);
+  r = {RT_SLABS, AIR_PACK_F32_SLABS, 0, fwd_pack_elems(p, ck, mt), 1, 1, 0};
+  if (!slab_bytes(p, 0, &r.pack_bytes)) return Route{};
+  if (!pro && !res) r.parts = fwd_ksplit(p, ck, mt);  // (plain convolutions only: run_fwd)
+  if (r.parts > 1) r.ws_floats += (size_t)r.parts * p->B * p->Cout * p->Ho * p->Wo;  // the slices' copies of y behind the slab
+  return r;
+}
+
+static Route dgrad_route(const AirConv2d* p) {
+  Route r = {};
+  if (!generic_ok(p) || wino_route(p, 1, &r)) return r;
+  r = {RT_SLABS, AIR_PACK_F32_SLABS, 0, packed_dgrad_elems(p), 1, 1, 0};  // (one slab at a time, each within this)
+  if (!slab_bytes(p, 1, &r.pack_bytes)) return Route{};
+  return r;
+}
+
+// workspace of the Winograd weight gradient on zero-padded x: the 64-channel copy of x, the partials, the 64-channel dW
+struct WinoPadWs {
+  size_t xpad, w64;
+  int nsplit;
+  size_t floats() const { return xpad + (size_t)(nsplit + 1) * w64; }
+};
+static WinoPadWs wino_pad_ws(const AirConv2d* p) {
+  return {((size_t)p->B * 64 * p->H * p->W + 63) / 64 * 64, (size_t)p->Cout * 64 * 9,
+          air_wino_wgrad_nsplit(p->B, 64, p->H, p->W, p->Cout)};
+}
+
+static Route wgrad_route(const AirConv2d* p, bool pro) {
+  Route r = {};
+  if (direct_ok(p)) {
+    if (pro) return r;
+    r.kind = RT_DIRECT; r.parts = p->B * p->Ho; r.taps = 1;
+  } else if (!generic_ok(p)) {
+    return r;
+  } else if (!pro && wino_shape(p) && air_wino_wgrad_ok(p->B, p->Cin, p->H, p->W, p->Cout)) {
+    r.kind = RT_WG_WINO; r.parts = air_wino_wgrad_nsplit(p->B, p->Cin, p->H, p->W, p->Cout); r.taps = 9;
+  } else if (!pro && bf3_wgrad_ok(p)) {
+    r.kind = RT_BF3; r.parts = air_bf3_s2w_nseg(p->B, p->Cin, p->Ho, p->Wo, p->Cout); r.taps = 9;
+  } else if (skinny3_wgrad_ok(p)) {
+    r.kind = RT_WG_SKINNY3; r.parts = skinny3_wgrad_parts(p); r.taps = 9;
+  } else if (!pro && wino_pad_wgrad(p)) {
+    const WinoPadWs l = wino_pad_ws(p);
+    return {RT_WG_WINO_PAD, AIR_PACK_NONE, 0, l.floats(), l.nsplit, 9, 0};
+  } else if (const int nch = skinny_wgrad_chunks(p)) {
+    r.kind = RT_WG_SKINNY1; r.parts = p->B * nch; r.taps = 1;
+  } else {
+    r.kind = RT_WG_SPLITK; r.parts = wgrad_nsplit(wgrad_geom(p)); r.taps = p->KH * p->KW;
+  }
+  r.ws_floats = (size_t)r.parts * p->Cout * p->Cin * p->KH * p->KW;
+  return r;
+}
+
+// the largest need over the passes of the layer, with and without the operands that change a route
+size_t air_conv2d_ws_bytes(const AirConv2d* p) {
+  if (!p || !shape_ok(p)) return 0;
+  const Route routes[] = {fwd_route(p, false, false), fwd_route(p, false, true), fwd_route(p, true, false),
+                          dgrad_route(p), wgrad_route(p, false), wgrad_route(p, true)};
+  size_t need = 0;
+  bool served = false;
+  for (const Route& r : routes) {
+    served = served || r.kind != RT_NONE;
+    if (r.ws_floats > need) need = r.ws_floats;
+  }
+  return served ? need * sizeof(float) + 256 : 0;
+}
+
+// air_conv2d_prepack serves the plain forward (pass 0) or the data gradient (pass 1)
+static Route pack_route(const AirConv2d* p, int pass) { return pass ? dgrad_route(p) : fwd_route(p, false, false); }
+
+size_t air_conv2d_prepack_bytes(const AirConv2d* p, int pass) {
+  return p && shape_ok(p) ? pack_route(p, pass).pack_bytes : 0;
 }
 
 // Which layout air_conv2d_prepack(p, ., pass) writes under the CURRENT dispatch options (a buffer packed under
 // other options - or the split-bf16 planes handed to a call that takes the f32 slabs - must be refused, not walked).
 int air_conv2d_prepack_layout(const AirConv2d* p, int pass) {
-  if (!p || !shape_ok(p)) return AIR_PACK_NONE;
-  const int kind = wino_kind(p, pass);
-  if (kind == 4) return AIR_PACK_WINO4;
-  if (kind == 2) return AIR_PACK_WINO2;
-  if (pass == 0 && bf3_fwd_ok(p)) return AIR_PACK_BF3;
-  return generic_pack_ok(p, pass) ? AIR_PACK_F32_SLABS : AIR_PACK_NONE;
+  return p && shape_ok(p) ? pack_route(p, pass).layout : AIR_PACK_NONE;
 }
 
 int air_conv2d_prepack(const AirConv2d* p, const float* w, int pass, void* out, size_t out_bytes, air_stream_t stream) {
   if (!p || !w || !out || !shape_ok(p)) return AIR_EINVAL;
-  const size_t need = air_conv2d_prepack_bytes(p, pass);
-  if (need == 0) return AIR_EUNSUPPORTED;
-  if (out_bytes < need) return AIR_EWORKSPACE;
+  const Route r = pack_route(p, pass);
+  if (r.pack_bytes == 0) return AIR_EUNSUPPORTED;
+  if (out_bytes < r.pack_bytes) return AIR_EWORKSPACE;
   const int M = pass ? p->Cin : p->Cout, Kc = pass ? p->Cout : p->Cin;
   float* up = reinterpret_cast<float*>(out);
-  const int kind = wino_kind(p, pass);
-  if (kind == 0 && pass == 0 && bf3_fwd_ok(p)) return air_bf3_s2_weights(w, nullptr, out, p->Cout, p->Cin, air_stream(stream));
-  if (kind == 0) {  // the direct kernels' slabs, in the order fwd_generic / dgrad_generic consume them
-    PackScope collect(PK_COLLECT, up);
-    float* none = nullptr;
-    return pass ? dgrad_generic(p, nullptr, w, nullptr, nullptr, none, air_stream(stream))
-                : fwd_generic(p, nullptr, w, nullptr, nullptr, nullptr, 0, nullptr, none, air_stream(stream));
+  hipStream_t st = air_stream(stream);
+  switch (r.layout) {
+    case AIR_PACK_WINO4: return air_wino4_weights(w, up, M, Kc, p->H, pass, st, true);
+    case AIR_PACK_WINO2: return air_wino_weights(w, up, M, Kc, pass, st);
+    case AIR_PACK_BF3: return air_bf3_s2_weights(w, nullptr, out, p->Cout, p->Cin, st);
+    default: {  // the direct kernels' slabs, in the order fwd_generic / dgrad_generic consume them
+      PackScope collect(PK_COLLECT, up);
+      float* none = nullptr;
+      return pass ? dgrad_generic(p, nullptr, w, nullptr, nullptr, none, st)
+                  : fwd_generic(p, nullptr, w, nullptr, nullptr, nullptr, 0, nullptr, none, st, 1);
+    }
   }
-  return kind == 4 ? air_wino4_weights(w, up, M, Kc, p->H, pass, air_stream(stream), true)
-                   : air_wino_weights(w, up, M, Kc, pass, air_stream(stream));
 }
 
 size_t air_conv2d_fwd_stats_bytes(const AirConv2d* p) {
-  if (!p || !shape_ok(p) || direct_ok(p) || !generic_ok(p)) return 0;
-  if (!wino_shape(p) || !air_wino4_ok(p->B, p->Cin, p->H, p->W, p->Cout) || p->Cout % 32 != 0) return 0;
-  return air_wino4_stats_bytes(p->B, p->H, p->W, p->Cout);
+  return p && shape_ok(p) ? fwd_route(p, false, false).bn_bytes : 0;
 }
 
 int air_conv2d_fwd_pre(const AirConv2d* p, const float* x, const float* w, const void* w_packed, float* y,
@@ -2045,61 +2077,48 @@ int air_conv2d_fwd_pre(const AirConv2d* p, const float* x, const float* w, const
                        double* stats, void* ws, size_t ws_bytes, air_stream_t stream) {
   if (!p || !x || !w || !y || !shape_ok(p)) return AIR_EINVAL;
   if ((in_scale == nullptr) != (in_shift == nullptr)) return AIR_EINVAL;
+  // fused prologue = BatchNorm-apply + ReLU together (the pre-activation block), or none
+  const bool pro = in_scale != nullptr;
+  if (pro != (relu != 0)) return AIR_EUNSUPPORTED;
+  const Route r = fwd_route(p, pro, residual != nullptr);
   // fused BatchNorm statistics: from the Winograd F(4x4 / 3x4, 3x3) epilogue only (air_conv2d_fwd_stats_bytes says
   // whether this layer takes that path under the current dispatch options)
-  if (stats != nullptr && air_conv2d_fwd_stats_bytes(p) == 0) return AIR_EUNSUPPORTED;
-  if (stats != nullptr && in_scale != nullptr) return AIR_EUNSUPPORTED;
+  if (r.kind == RT_NONE || (stats != nullptr && r.bn_bytes == 0)) return AIR_EUNSUPPORTED;
+  if (r.ws_floats > 0 && (!ws || ws_bytes < r.ws_floats * sizeof(float))) return AIR_EWORKSPACE;
   hipStream_t st = air_stream(stream);
-  if (direct_ok(p)) {
-    if (in_scale || relu || residual) return AIR_EUNSUPPORTED;
-    DirectArgs a = {x, w, y, nullptr, nullptr, p->B, p->Cin, p->H, p->W, p->Cout, p->KH, p->KW,
-                    p->sh, p->sw, p->ph, p->pw, p->Ho, p->Wo};
-    hipLaunchKernelGGL(conv_direct_fwd_kernel, dim3(grid_for((size_t)p->B * p->Ho * p->Wo)),
-                       dim3(256), 0, st, a);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (!generic_ok(p)) return AIR_EUNSUPPORTED;
-  // fused prologue = BatchNorm-apply + ReLU together (the pre-activation block), or none
-  if ((in_scale != nullptr) != (relu != 0)) return AIR_EUNSUPPORTED;
-  if (in_scale != nullptr && p->Cin > MAXC) return AIR_EUNSUPPORTED;
-  const size_t wsz = (size_t)p->Cout * p->Cin * p->KH * p->KW;
-  if (!ws || ws_bytes < wsz * sizeof(float)) return AIR_EWORKSPACE;
-  float* wp = reinterpret_cast<float*>(ws);
-  if (in_scale == nullptr && wino_shape(p) && air_wino4_ok(p->B, p->Cin, p->H, p->W, p->Cout)) {
-    if (ws_bytes < air_wino4_packed_elems(p->Cout, p->Cin) * sizeof(float)) return AIR_EWORKSPACE;
-    if (w_packed)  // transformed earlier (air_conv2d_prepack): no weights kernel in front of the conv
-      return air_wino4_conv(x, nullptr, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0,
-                            const_cast<float*>(reinterpret_cast<const float*>(w_packed)), conv_flops(p), st,
-                            reinterpret_cast<float*>(stats));
-    return air_wino4_conv(x, w, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0, wp,
-                          conv_flops(p), st, reinterpret_cast<float*>(stats));
-  }
-  if (in_scale == nullptr && wino_shape(p) && air_wino_ok(p->B, p->Cin, p->H, p->W, p->Cout)) {
-    if (ws_bytes < air_wino_packed_elems(p->Cout, p->Cin) * sizeof(float)) return AIR_EWORKSPACE;
-    if (w_packed)
-      return air_wino_conv(x, nullptr, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0,
-                           const_cast<float*>(reinterpret_cast<const float*>(w_packed)), conv_flops(p), st);
-    return air_wino_conv(x, w, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0, wp,
-                         conv_flops(p), st);
-  }
-  if (in_scale == nullptr && residual == nullptr && bf3_fwd_ok(p)) {
-    const size_t need = air_bf3_s2_packed_bytes(p->Cout, p->Cin, false);
-    if (w_packed == nullptr) {
-      if (ws_bytes < need) return AIR_EWORKSPACE;
-      const int rc = air_bf3_s2_weights(w, nullptr, ws, p->Cout, p->Cin, st);
-      if (rc != AIR_OK) return rc;
+  // transformed earlier (air_conv2d_prepack): no weights kernel in front of the conv
+  float* up = w_packed ? const_cast<float*>(reinterpret_cast<const float*>(w_packed)) : reinterpret_cast<float*>(ws);
+  const float* wt = w_packed ? nullptr : w;
+  switch (r.kind) {
+    case RT_DIRECT: {
+      DirectArgs a = {x, w, y, nullptr, nullptr, p->B, p->Cin, p->H, p->W, p->Cout, p->KH, p->KW,
+                      p->sh, p->sw, p->ph, p->pw, p->Ho, p->Wo};
+      hipLaunchKernelGGL(conv_direct_fwd_kernel, dim3(grid_for((size_t)p->B * p->Ho * p->Wo)),
+                         dim3(256), 0, st, a);
+      AIR_CHECK_LAUNCH();
+      return AIR_OK;
     }
-    return air_bf3_s2_fwd(x, w_packed ? w_packed : ws, y, nullptr, p->B, p->Cin, p->H, p->W, p->Cout, p->Ho, p->Wo,
-                          conv_flops(p), st);
+    case RT_WINO4:
+      return air_wino4_conv(x, wt, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0, up, conv_flops(p), st,
+                            reinterpret_cast<float*>(stats));
+    case RT_WINO2:
+      return air_wino_conv(x, wt, y, residual, p->B, p->Cin, p->H, p->W, p->Cout, 0, up, conv_flops(p), st);
+    case RT_BF3: {
+      if (w_packed == nullptr) {
+        const int rc = air_bf3_s2_weights(w, nullptr, ws, p->Cout, p->Cin, st);
+        if (rc != AIR_OK) return rc;
+      }
+      return air_bf3_s2_fwd(x, up, y, nullptr, p->B, p->Cin, p->H, p->W, p->Cout, p->Ho, p->Wo, conv_flops(p), st);
+    }
+    default: {
+      // w_packed holds what the plain forward consumes: a call with a prologue or a residual whose plain form runs on
+      // Winograd transforms or split-bf16 planes packs from w instead
+      const bool mine = w_packed != nullptr &&
+                        ((!pro && !residual) || fwd_route(p, false, false).layout == AIR_PACK_F32_SLABS);
+      PackScope use(mine ? PK_USE : PK_RUN, mine ? up : nullptr);
+      return fwd_generic(p, x, w, y, in_scale, in_shift, relu, residual, reinterpret_cast<float*>(ws), st, r.parts);
+    }
   }
-  // slabs from air_conv2d_prepack (a Winograd-shaped layer's buffer is not ours; neither are the split-bf16 planes that
-  // prepack writes for a bf3-eligible layer - a call with a prologue or a residual lands here and packs from w instead)
-  if (w_packed != nullptr && wino_kind(p, 0) == 0 && !bf3_fwd_ok(p)) {
-    PackScope use(PK_USE, const_cast<float*>(reinterpret_cast<const float*>(w_packed)));
-    return fwd_generic(p, x, w, y, in_scale, in_shift, relu, residual, wp, st, ws_bytes / sizeof(float));
-  }
-  return fwd_generic(p, x, w, y, in_scale, in_shift, relu, residual, wp, st, ws_bytes / sizeof(float));
 }
 
 // ---- forward of a stride-2 PreActBlock's two convolutions on the same input (resnet.py:56-66) in one launch
@@ -2140,36 +2159,32 @@ int air_conv2d_fwd(const AirConv2d* p, const float* x, const float* w, float* y,
   return air_conv2d_fwd_pre(p, x, w, nullptr, y, in_scale, in_shift, relu, residual, stats, ws, ws_bytes, stream);
 }
 
+// the data gradient on its route; sums / bn: the BatchNorm-backward epilogue of the F(4x4) kernel (air_conv2d_dgrad_bn)
+static int dgrad_on_route(const AirConv2d* p, const Route& r, const float* dy, const float* w, const void* w_packed,
+                          float* dx, const float* accumulate, float* sums, const float* const* bn, void* ws,
+                          size_t ws_bytes, hipStream_t st) {
+  if (r.kind == RT_NONE || (sums != nullptr && r.bn_bytes == 0)) return AIR_EUNSUPPORTED;
+  if (!ws || ws_bytes < r.ws_floats * sizeof(float)) return AIR_EWORKSPACE;
+  float* up = w_packed ? const_cast<float*>(reinterpret_cast<const float*>(w_packed)) : reinterpret_cast<float*>(ws);
+  const float* wt = w_packed ? nullptr : w;
+  // roles swap: "input" channels = Cout, "output" channels = Cin
+  switch (r.kind) {
+    case RT_WINO4:
+      return air_wino4_conv(dy, wt, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1, up, conv_flops(p), st, sums, bn);
+    case RT_WINO2:
+      return air_wino_conv(dy, wt, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1, up, conv_flops(p), st);
+    default: {
+      PackScope use(w_packed ? PK_USE : PK_RUN, w_packed ? up : nullptr);
+      return dgrad_generic(p, dy, w, dx, accumulate, reinterpret_cast<float*>(ws), st);
+    }
+  }
+}
+
 int air_conv2d_dgrad_pre(const AirConv2d* p, const float* dy, const float* w, const void* w_packed, float* dx,
                          const float* accumulate, void* ws, size_t ws_bytes, air_stream_t stream) {
   if (!p || !dy || !w || !dx || !shape_ok(p)) return AIR_EINVAL;
-  if (!generic_ok(p)) return AIR_EUNSUPPORTED;
-  hipStream_t st = air_stream(stream);
-  const size_t wsz = packed_dgrad_elems(p);
-  if (!ws || ws_bytes < wsz * sizeof(float)) return AIR_EWORKSPACE;
-  float* wp = reinterpret_cast<float*>(ws);
-  // roles swap: "input" channels = Cout, "output" channels = Cin
-  if (wino_shape(p) && air_wino4_ok(p->B, p->Cout, p->H, p->W, p->Cin)) {
-    if (ws_bytes < air_wino4_packed_elems(p->Cin, p->Cout) * sizeof(float)) return AIR_EWORKSPACE;
-    if (w_packed)
-      return air_wino4_conv(dy, nullptr, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1,
-                            const_cast<float*>(reinterpret_cast<const float*>(w_packed)), conv_flops(p), st);
-    return air_wino4_conv(dy, w, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1, wp,
-                          conv_flops(p), st);
-  }
-  if (wino_shape(p) && air_wino_ok(p->B, p->Cout, p->H, p->W, p->Cin)) {
-    if (ws_bytes < air_wino_packed_elems(p->Cin, p->Cout) * sizeof(float)) return AIR_EWORKSPACE;
-    if (w_packed)
-      return air_wino_conv(dy, nullptr, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1,
-                           const_cast<float*>(reinterpret_cast<const float*>(w_packed)), conv_flops(p), st);
-    return air_wino_conv(dy, w, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1, wp,
-                         conv_flops(p), st);
-  }
-  if (w_packed != nullptr && wino_kind(p, 1) == 0) {
-    PackScope use(PK_USE, const_cast<float*>(reinterpret_cast<const float*>(w_packed)));
-    return dgrad_generic(p, dy, w, dx, accumulate, wp, st);
-  }
-  return dgrad_generic(p, dy, w, dx, accumulate, wp, st);
+  return dgrad_on_route(p, dgrad_route(p), dy, w, w_packed, dx, accumulate, nullptr, nullptr, ws, ws_bytes,
+                        air_stream(stream));
 }
 
 int air_conv2d_dgrad(const AirConv2d* p, const float* dy, const float* w, float* dx,
@@ -2178,10 +2193,7 @@ int air_conv2d_dgrad(const AirConv2d* p, const float* dy, const float* w, float*
 }
 
 size_t air_conv2d_dgrad_bn_sums_bytes(const AirConv2d* p) {
-  if (!p || !shape_ok(p) || !generic_ok(p)) return 0;
-  // the Winograd F(3x4 / 4x4, 3x3) data-gradient kernel, whole 32-channel slabs of dx
-  if (!wino_shape(p) || !air_wino4_ok(p->B, p->Cout, p->H, p->W, p->Cin) || p->Cin % 32 != 0) return 0;
-  return air_wino4_stats_bytes(p->B, p->H, p->W, p->Cin);
+  return p && shape_ok(p) ? dgrad_route(p).bn_bytes : 0;
 }
 
 int air_conv2d_dgrad_bn(const AirConv2d* p, const float* dy, const float* w, const void* w_packed, float* dx,
@@ -2190,17 +2202,11 @@ int air_conv2d_dgrad_bn(const AirConv2d* p, const float* dy, const float* w, con
                         air_stream_t stream) {
   if (!p || !dy || !w || !dx || !shape_ok(p) || !bn_x || !bn_mean || !bn_invstd || !bn_gamma || !bn_beta || !sums)
     return AIR_EINVAL;
-  if (air_conv2d_dgrad_bn_sums_bytes(p) == 0) return AIR_EUNSUPPORTED;
-  if (ws_bytes < air_wino4_packed_elems(p->Cin, p->Cout) * sizeof(float) || !ws) return AIR_EWORKSPACE;
   const float* bn[5] = {bn_x, bn_mean, bn_invstd, bn_gamma, bn_beta};
-  hipStream_t st = air_stream(stream);
-  if (w_packed)
-    return air_wino4_conv(dy, nullptr, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1,
-                          const_cast<float*>(reinterpret_cast<const float*>(w_packed)), conv_flops(p), st,
-                          reinterpret_cast<float*>(sums), bn);
-  return air_wino4_conv(dy, w, dx, accumulate, p->B, p->Cout, p->H, p->W, p->Cin, 1, reinterpret_cast<float*>(ws),
-                        conv_flops(p), st, reinterpret_cast<float*>(sums), bn);
+  return dgrad_on_route(p, dgrad_route(p), dy, w, w_packed, dx, accumulate, reinterpret_cast<float*>(sums), bn, ws,
+                        ws_bytes, air_stream(stream));
 }
+
 
 static size_t s2d_pack_elems(const AirConv2d* p, int taps) {
   const int bm = 32 * s2d_mt(p);
@@ -2229,15 +2235,10 @@ int air_conv2d_dgrad_s2_pair_prepack(const AirConv2d* p, const float* w, const f
   const int mt = s2d_mt(p);
   float* w9 = reinterpret_cast<float*>(out);
   float* w1 = w9 + s2d_pack_elems(p, 9);
-  TapSel s9, s1;
-  s9.n = 9;
-  for (int t = 0; t < 9; ++t) s9.idx[t] = t;
-  s1.n = 1;
-  s1.idx[0] = 0;
   PackScope collect(PK_COLLECT, w9);  // (the two slabs back to back in `out`; deferred like any prepack between begin / flush)
-  int rc = pack(w, w9, p->Cout, p->Cin, 9, 1, S2D_CK, mt, s9, st);
+  int rc = pack(w, w9, p->Cout, p->Cin, 9, 1, S2D_CK, mt, tap_run(9, 0, 1), st);
   if (rc != AIR_OK) return rc;
-  return pack(w_sc, w1, p->Cout, p->Cin, 1, 1, S2D_CK, mt, s1, st);
+  return pack(w_sc, w1, p->Cout, p->Cin, 1, 1, S2D_CK, mt, tap_run(1, 0, 1), st);
 }
 
 int air_conv2d_prepack_begin(void) {
@@ -2290,126 +2291,100 @@ int air_conv2d_wgrad(const AirConv2d* p, const float* x, const float* dy, float*
                      size_t ws_bytes, air_stream_t stream) {
   if (!p || !x || !dy || !dw || !shape_ok(p)) return AIR_EINVAL;
   if ((in_scale == nullptr) != (in_shift == nullptr)) return AIR_EINVAL;
+  const bool pro = in_scale != nullptr;
+  if (pro != (relu != 0)) return AIR_EUNSUPPORTED;  // BN-apply + ReLU together, or none
+  const Route r = wgrad_route(p, pro);
   hipStream_t st = air_stream(stream);
   const size_t wsz = (size_t)p->Cout * p->Cin * p->KH * p->KW;
-  if (direct_ok(p)) {
-    if (in_scale || relu) return AIR_EUNSUPPORTED;
-    const int rows = p->B * p->Ho;
-    if (!ws || ws_bytes < (size_t)rows * wsz * sizeof(float)) return AIR_EWORKSPACE;
-    DirectArgs a = {x, nullptr, nullptr, dy, reinterpret_cast<float*>(ws), p->B, p->Cin, p->H,
-                    p->W, p->Cout, p->KH, p->KW, p->sh, p->sw, p->ph, p->pw, p->Ho, p->Wo};
-    const int npair = p->Cout * p->Cin * p->KH;
-    int nseg = npair > 0 && npair <= 512 ? 512 / npair : 1;
-    if (nseg > 4) nseg = 4;
-    // the staged rows and, once they are dead, the per-segment sums red[nseg][npair][KW] share the allocation:
-    // short rows (W <= 48 for the ResNet's conv1) make the sums the larger of the two
-    const size_t stage_f = (size_t)p->Cout * ((p->Wo + 3) & ~3) +
-                           (size_t)p->Cin * p->KH * (((p->W + 2 * p->pw + 3) & ~3) + 4);
-    const size_t red_f = (size_t)nseg * npair * p->KW;
-    const size_t lds = (stage_f > red_f ? stage_f : red_f) * sizeof(float);
-    const int use_rows = air_opt(AIR_OPT_DIRECT_WGRAD_ROWS);
-    if (use_rows && p->KW <= DIRECT_KW_MAX && npair <= 512 && lds <= 150 * 1024) {
-      const int nthr = (npair * nseg + 63) / 64 * 64;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_wgrad_rows_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return AIR_ELAUNCH;
-      hipLaunchKernelGGL(conv_direct_wgrad_rows_kernel, dim3(rows), dim3(nthr), lds, st, a, nseg);
-    } else {
-      hipLaunchKernelGGL(conv_direct_wgrad_kernel, dim3(rows), dim3(256), 0, st, a);
-    }
-    AIR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, rows)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(ws), dw, wsz, rows, 1);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (!generic_ok(p)) return AIR_EUNSUPPORTED;
-  if ((in_scale != nullptr) != (relu != 0)) return AIR_EUNSUPPORTED;  // BN-apply + ReLU together, or none
-  if (in_scale == nullptr && wino_shape(p) && air_wino_wgrad_ok(p->B, p->Cin, p->H, p->W, p->Cout)) {
-    const int nsplit = air_wino_wgrad_nsplit(p->B, p->Cin, p->H, p->W, p->Cout);
-    if (!ws || ws_bytes < (size_t)nsplit * wsz * sizeof(float)) return AIR_EWORKSPACE;
-    int rc = air_wino_wgrad_partials(x, dy, reinterpret_cast<float*>(ws), p->B, p->Cin, p->H, p->W,
-                                     p->Cout, conv_flops(p), st);
-    if (rc != AIR_OK) return rc;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, nsplit)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(ws), dw, wsz, nsplit, 9);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (in_scale == nullptr && bf3_wgrad_ok(p)) {  // split-bf16 stride-2 weight gradient (conv_bf3.hip)
-    const int nseg = air_bf3_s2w_nseg(p->B, p->Cin, p->Ho, p->Wo, p->Cout);
-    if (!ws || ws_bytes < (size_t)nseg * wsz * sizeof(float)) return AIR_EWORKSPACE;
-    int rc = air_bf3_s2w_partials(x, dy, reinterpret_cast<float*>(ws), p->B, p->Cin, p->H, p->W, p->Cout, p->Ho, p->Wo,
-                                  conv_flops(p), st);
-    if (rc != AIR_OK) return rc;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, nseg)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(ws), dw, wsz, nseg, 9);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (skinny3_wgrad_ok(p)) {
-    const int nparts = skinny3_wgrad_parts(p);
-    if (!ws || ws_bytes < (size_t)nparts * wsz * sizeof(float)) return AIR_EWORKSPACE;
-    Skinny3Wg a = {x, dy, reinterpret_cast<float*>(ws), in_scale, in_shift, (size_t)p->Cin * p->H * p->W,
-                   (size_t)p->Cout * p->H * p->W, p->B, p->H, p->W};
-    {
-      AirProfScope ps(AIR_K_CONV_WG_331, conv_flops(p), st);
-      if (in_scale)
-        hipLaunchKernelGGL((conv_wgrad_3x3_skinny_kernel<4, true>), dim3(nparts), dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_wgrad_3x3_skinny_kernel<4, false>), dim3(nparts), dim3(256), 0, st, a);
+  const size_t xb = (size_t)p->Cin * p->H * p->W, yb = (size_t)p->Cout * p->Ho * p->Wo;
+  switch (r.kind) {
+    case RT_DIRECT:
+      return wgrad_parts(ws, ws_bytes, r.parts, wsz, r.taps, dw, st, [&](float* partial) -> int {
+        DirectArgs a = {x, nullptr, nullptr, dy, partial, p->B, p->Cin, p->H,
+                        p->W, p->Cout, p->KH, p->KW, p->sh, p->sw, p->ph, p->pw, p->Ho, p->Wo};
+        const int npair = p->Cout * p->Cin * p->KH;
+        int nseg = npair > 0 && npair <= 512 ? 512 / npair : 1;
+        if (nseg > 4) nseg = 4;
+        // the staged rows and, once they are dead, the per-segment sums red[nseg][npair][KW] share the allocation:
+        // short rows (W <= 48 for the ResNet's conv1) make the sums the larger of the two
+        const size_t stage_f = (size_t)p->Cout * ((p->Wo + 3) & ~3) +
+                               (size_t)p->Cin * p->KH * (((p->W + 2 * p->pw + 3) & ~3) + 4);
+        const size_t red_f = (size_t)nseg * npair * p->KW;
+        const size_t lds = (stage_f > red_f ? stage_f : red_f) * sizeof(float);
+        const int use_rows = air_opt(AIR_OPT_DIRECT_WGRAD_ROWS);
+        if (use_rows && p->KW <= DIRECT_KW_MAX && npair <= 512 && lds <= 150 * 1024) {
+          const int nthr = (npair * nseg + 63) / 64 * 64;
+          if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_direct_wgrad_rows_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return AIR_ELAUNCH;
+          hipLaunchKernelGGL(conv_direct_wgrad_rows_kernel, dim3(r.parts), dim3(nthr), lds, st, a, nseg);
+        } else {
+          hipLaunchKernelGGL(conv_direct_wgrad_kernel, dim3(r.parts), dim3(256), 0, st, a);
+        }
+        AIR_CHECK_LAUNCH();
+        return AIR_OK;
+      });
+    case RT_WG_WINO:
+      return wgrad_parts(ws, ws_bytes, r.parts, wsz, r.taps, dw, st, [&](float* partial) -> int {
+        return air_wino_wgrad_partials(x, dy, partial, p->B, p->Cin, p->H, p->W, p->Cout, conv_flops(p), st);
+      });
+    case RT_BF3:  // split-bf16 stride-2 weight gradient (conv_bf3.hip)
+      return wgrad_parts(ws, ws_bytes, r.parts, wsz, r.taps, dw, st, [&](float* partial) -> int {
+        return air_bf3_s2w_partials(x, dy, partial, p->B, p->Cin, p->H, p->W, p->Cout, p->Ho, p->Wo, conv_flops(p), st);
+      });
+    case RT_WG_SKINNY3:
+      return wgrad_parts(ws, ws_bytes, r.parts, wsz, r.taps, dw, st, [&](float* partial) -> int {
+        Skinny3Wg a = {x, dy, partial, in_scale, in_shift, xb, yb, p->B, p->H, p->W};
+        AirProfScope ps(AIR_K_CONV_WG_331, conv_flops(p), st);
+        if (pro)
+          hipLaunchKernelGGL((conv_wgrad_3x3_skinny_kernel<4, true>), dim3(r.parts), dim3(256), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv_wgrad_3x3_skinny_kernel<4, false>), dim3(r.parts), dim3(256), 0, st, a);
+        AIR_CHECK_LAUNCH();
+        return AIR_OK;
+      });
+    case RT_WG_WINO_PAD: {
+      if (!ws || ws_bytes < r.ws_floats * sizeof(float)) return AIR_EWORKSPACE;
+      const WinoPadWs l = wino_pad_ws(p);
+      const size_t hw = (size_t)p->H * p->W;
+      float* xpad = reinterpret_cast<float*>(ws);
+      float* partial = xpad + l.xpad;
+      float* dw64 = partial + (size_t)l.nsplit * l.w64;
+      if (hipMemsetAsync(xpad, 0, l.xpad * sizeof(float), st) != hipSuccess) return AIR_ELAUNCH;
+      hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for((size_t)p->Cin * hw), p->B), dim3(256), 0, st, xpad,
+                         (size_t)64 * hw, x, (size_t)p->Cin * hw, (size_t)p->Cin * hw);
       AIR_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, nparts)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(ws), dw, wsz, nparts, 9);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (in_scale == nullptr && wino_pad_wgrad(p)) {
-    const size_t hw = (size_t)p->H * p->W;
-    const size_t xpad_n = ((size_t)p->B * 64 * hw + 63) / 64 * 64;
-    const int nsplit = air_wino_wgrad_nsplit(p->B, 64, p->H, p->W, p->Cout);
-    const size_t w64 = (size_t)p->Cout * 64 * 9;
-    if (!ws || ws_bytes < (xpad_n + (size_t)(nsplit + 1) * w64) * sizeof(float)) return AIR_EWORKSPACE;
-    float* xpad = reinterpret_cast<float*>(ws);
-    float* partial = xpad + xpad_n;
-    float* dw64 = partial + (size_t)nsplit * w64;
-    if (hipMemsetAsync(xpad, 0, xpad_n * sizeof(float), st) != hipSuccess) return AIR_ELAUNCH;
-    hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for((size_t)p->Cin * hw), p->B), dim3(256), 0, st, xpad,
-                       (size_t)64 * hw, x, (size_t)p->Cin * hw, (size_t)p->Cin * hw);
-    AIR_CHECK_LAUNCH();
-    int rc = air_wino_wgrad_partials(xpad, dy, partial, p->B, 64, p->H, p->W, p->Cout, conv_flops(p), st);
-    if (rc != AIR_OK) return rc;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(w64, nsplit)), dim3(256), 0, st, partial, dw64, w64, nsplit, 9);
-    AIR_CHECK_LAUNCH();
-    // dw[co][ci < Cin][tap] = dw64[co][ci][tap]: the first Cin * 9 floats of every 64 * 9 row
-    hipLaunchKernelGGL(copy_rows_kernel, dim3(1, p->Cout), dim3(256), 0, st, dw, (size_t)p->Cin * 9, dw64,
-                       (size_t)64 * 9, (size_t)p->Cin * 9);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
-  }
-  if (const int nch = skinny_wgrad_chunks(p)) {
-    const int nparts = p->B * nch;
-    if (!ws || ws_bytes < (size_t)nparts * wsz * sizeof(float)) return AIR_EWORKSPACE;
-    SkinnyWg a = {x, dy, reinterpret_cast<float*>(ws), in_scale, in_shift, (size_t)p->Cin * p->H * p->W,
-                  (size_t)p->Cout * p->H * p->W, p->H * p->W, skinny_wgrad_chunk_px(p, nch), nch};
-    {
-      AirProfScope ps(AIR_K_CONV_WG_111, conv_flops(p), st);
-      if (in_scale)
-        hipLaunchKernelGGL((conv_wgrad_1x1_skinny_kernel<4, 1, true>), dim3(nparts), dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_wgrad_1x1_skinny_kernel<4, 1, false>), dim3(nparts), dim3(256), 0, st, a);
+      const int rc = wgrad_parts(partial, ws_bytes - l.xpad * sizeof(float), l.nsplit, l.w64, r.taps, dw64, st,
+                                 [&](float* part) -> int {
+        return air_wino_wgrad_partials(xpad, dy, part, p->B, 64, p->H, p->W, p->Cout, conv_flops(p), st);
+      });
+      if (rc != AIR_OK) return rc;
+      // dw[co][ci < Cin][tap] = dw64[co][ci][tap]: the first Cin * 9 floats of every 64 * 9 row
+      hipLaunchKernelGGL(copy_rows_kernel, dim3(1, p->Cout), dim3(256), 0, st, dw, (size_t)p->Cin * 9, dw64,
+                         (size_t)64 * 9, (size_t)p->Cin * 9);
       AIR_CHECK_LAUNCH();
+      return AIR_OK;
     }
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(reduce_grid(wsz, nparts)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(ws), dw, wsz, nparts, 1);
-    AIR_CHECK_LAUNCH();
-    return AIR_OK;
+    case RT_WG_SKINNY1:
+      return wgrad_parts(ws, ws_bytes, r.parts, wsz, r.taps, dw, st, [&](float* partial) -> int {
+        const int nch = r.parts / p->B;
+        SkinnyWg a = {x, dy, partial, in_scale, in_shift, xb, yb, p->H * p->W, skinny_wgrad_chunk_px(p, nch), nch};
+        AirProfScope ps(AIR_K_CONV_WG_111, conv_flops(p), st);
+        if (pro)
+          hipLaunchKernelGGL((conv_wgrad_1x1_skinny_kernel<4, 1, true>), dim3(r.parts), dim3(256), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv_wgrad_1x1_skinny_kernel<4, 1, false>), dim3(r.parts), dim3(256), 0, st, a);
+        AIR_CHECK_LAUNCH();
+        return AIR_OK;
+      });
+    case RT_WG_SPLITK:
+      return run_wgrad(wgrad_geom(p), x, dy, dw, in_scale, in_shift, relu, ws, ws_bytes, conv_flops(p), st);
+    default:
+      return AIR_EUNSUPPORTED;
   }
-  WgradGeom g = {p->B, p->Cin, p->H, p->W, p->Cout, p->KH, p->KW, p->sh, p->ph, p->pw, p->Ho, p->Wo,
-                 1, (size_t)p->Cin * p->H * p->W, (size_t)p->Cout * p->Ho * p->Wo};
-  return run_wgrad(g, x, dy, dw, in_scale, in_shift, relu, ws, ws_bytes, conv_flops(p), st);
 }
+
+
 
 // ------------------------------------------------------------------ conv1d
 // nn.Conv1d (stride 1) of ecapa_tdnn.py (:39,:46,:55,:111,:118,:140,:143) seen as an H = 1

@@ -91,6 +91,57 @@ def test_conv_workspace_queries(lib):
     assert lib.air_bn_ws_bytes(ctypes.c_int(64), ctypes.c_int(64), ctypes.c_int(13500)) > 0
 
 
+ROUTE_OPTIONS = [{}, {"NO_WINOGRAD": 1}, {"NO_WINOGRAD": 2}, {"NO_WINOGRAD": 3}, {"NO_WINO4": 1}, {"CONV_S2": 0},
+                 {"CONV_S2": 7}, {"CONV_S2": 31}, {"SKINNY_WGRAD": 0}, {"CONV_MT": 1}, {"CONV_MT": 2}, {"WGRAD_WGS": 1},
+                 {"WGRAD_WGS": 1 << 20}, {"WINO_WGRAD_WGS": 1}, {"WINO_WGRAD_WGS": 1 << 20}]
+# (KH, KW, stride, padding): the five served forms, the stride-2 / pad-0 3x3 whose data gradient has no kernel, the
+# ResNet's conv1 and conv5, and a 5x5 nothing serves
+ROUTE_FORMS = [(3, 3, (1, 1), (1, 1)), (3, 3, (2, 2), (1, 1)), (1, 1, (1, 1), (0, 0)), (1, 1, (2, 2), (0, 0)),
+               (3, 3, (1, 1), (0, 1)), (3, 3, (2, 2), (0, 0)), (9, 3, (3, 1), (1, 1)), (5, 5, (1, 1), (2, 2))]
+ROUTE_CHANNELS = [(1, 16), (16, 64), (48, 64), (64, 64), (64, 128), (64, 192), (512, 64), (24, 24)]
+ROUTE_IMAGES = [(2, 6, 3), (2, 9, 12), (64, 3, 188), (8, 18, 750)]
+
+
+def test_conv_route_queries_agree_with_each_other(lib):
+    """The exported size / layout queries are fields of one route per pass (csrc/conv2d.hip: fwd_route, dgrad_route,
+    wgrad_route), so they cannot contradict each other, whatever the dispatch options."""
+    from asvspoof2021_air_amd import _hip
+    from asvspoof2021_air_amd._hip import AirConv2d
+    PACK_NONE, PACK_WINO4 = 0, 4
+    served = 0
+    for opts in ROUTE_OPTIONS:
+        with _hip.options(**opts):
+            for (KH, KW, (sh, sw), (ph, pw)) in ROUTE_FORMS:
+                for (Cin, Cout) in ROUTE_CHANNELS:
+                    for (B, H, W) in ROUTE_IMAGES:
+                        Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
+                        if Ho <= 0 or Wo <= 0:
+                            continue
+                        d = AirConv2d(B, Cin, H, W, Cout, KH, KW, sh, sw, ph, pw, Ho, Wo)
+                        what = (opts, [getattr(d, f[0]) for f in d._fields_])
+                        ws = lib.air_conv2d_ws_bytes(ctypes.byref(d))
+                        pack = [lib.air_conv2d_prepack_bytes(ctypes.byref(d), ctypes.c_int(k)) for k in (0, 1)]
+                        layout = [lib.air_conv2d_prepack_layout(ctypes.byref(d), ctypes.c_int(k)) for k in (0, 1)]
+                        fused = [lib.air_conv2d_fwd_stats_bytes(ctypes.byref(d)),
+                                 lib.air_conv2d_dgrad_bn_sums_bytes(ctypes.byref(d))]
+                        for k in (0, 1):
+                            assert (layout[k] != PACK_NONE) == (pack[k] > 0), (what, k, layout, pack)
+                            assert fused[k] == 0 or layout[k] == PACK_WINO4, (what, k, fused, layout)
+                            # a call without w_packed packs into the workspace
+                            assert ws == 0 or ws >= pack[k], (what, k, ws, pack)
+                        if ws == 0:
+                            assert pack == [0, 0] and fused == [0, 0], (what, pack, fused)
+                        # served: up to 16 output channels by the direct kernels; 3x3 and 1x1, stride 1 or 2, with whole
+                        # 64-channel output tiles and 8-channel input chunks, by the MFMA kernels; nothing else
+                        small = Cout <= 16 and Cout * Cin * KH * KW <= 16 * 27
+                        mfma = (KH, KW) in ((3, 3), (1, 1)) and Cin % 8 == 0 and Cout % 64 == 0
+                        assert (ws > 0) == (small or mfma), (what, ws)
+                        served += ws > 0
+                        bad = AirConv2d(B, Cin, H, W, Cout, KH, KW, sh, sw, ph, pw, Ho, Wo + 1)
+                        assert lib.air_conv2d_ws_bytes(ctypes.byref(bad)) == 0, what
+    assert served > 1000
+
+
 def test_product_path_refuses_cpu_tensors():
     """No CPU fallback anywhere on the product path."""
     from asvspoof2021_air_amd import _hip

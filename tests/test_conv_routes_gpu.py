@@ -11,7 +11,9 @@ batch.  So:
   ``reduce_partials_kernel`` followed) and hold it against fp64;
 * the dispatch options nothing else sets are swept, each held to its kernel's bound, with the alternative shown to run;
 * every ``*_kernel`` of the four convolution sources is launched by some case (or is on the allow-list with a reason);
-* the stride-2 weight gradients without a kernel instance are refused, not answered.
+* the stride-2 weight gradients without a kernel instance are refused, not answered;
+* every route runs on a workspace of exactly air_conv2d_ws_bytes(p) bytes between sentinels, and is refused one byte below
+  its own need.
 
 References: float64 F.conv2d on the GPU through ATen's own convolution (MIOpen off: it has no fp64 kernels), checked
 once against CPU float64.  Forward / data gradient are compared on the first, a middle and the last utterance (the
@@ -38,9 +40,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "asvspoof2021_air_amd", "csrc")
 CONV_SOURCES = ("conv2d.hip", "conv_wino.hip", "conv_wino4.hip", "conv_bf3.hip")
 # kernels of those sources that no case launches, with the reason
-ALLOW_UNLAUNCHED = {
-    "upsample2_kernel": "no caller: the stride-2 data gradient runs as four parity classes / one pass instead",
-}
+ALLOW_UNLAUNCHED = {}
 WRAPPED = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d_fwd_s2_pair", "conv2d_dgrad_s2_pair",
            "lcnn_conv1_fwd", "lcnn_conv1_wgrad")
 WINO_WGRAD_RTOL = 1e-5
@@ -696,6 +696,124 @@ def test_dispatch_option_holds_its_kernels_bound(ops, case):
     with _hip.options(**opts):
         names = replay(ops, sig)
     check_route(names, has, lacks, None, reduce)
+
+
+# ------------------------------------------------------------------------------------------------ workspace
+AIR_EWORKSPACE = -4
+W64, W128S2 = (64, 64, 3, 3), (128, 64, 3, 3)
+X_S2 = (2, 64, 9, 12)
+# One small descriptor per route, called through the C entry point on a workspace of exactly air_conv2d_ws_bytes(p)
+# bytes.  need: the floats the route itself checks for (csrc/conv2d.hip, fwd_route / dgrad_route / wgrad_route), written
+# out from the launch's own layout:
+# * Winograd transforms: Cout Cin 16 floats for F(2x2), Cout Cin 36 + 1024 for F(4x4); split-bf16 planes: 6 bytes a weight
+# * K-split forward, (64, 512, 1, 1) on 2 x 2 x 32 pixels: one workgroup, 16 chunks of 32 channels -> 2 slices; the slab
+#   and two copies of y
+# * data gradient slabs: Cin (to 64) x Cout (to 32) x taps
+# * weight gradients: partials x Cout Cin taps - 6 Winograd segments (2 x 3 tile rows x 1); 2 split-bf16 segments (10 rows
+#   in steps of 8); 10 and 8 split-K pixel tiles; min(B H, 256) = 8 skinny 3x3 rows; 2 x 1 skinny 1x1 chunks; B Ho = 4
+#   rows of conv1; on zero-padded x the 2 x 64 x 48 copy of x, 6 partials and the 64-channel dW
+# (id, op, x, w, stride, padding, flags, options, has kernels, lacks kernels, need in floats)
+WS_CASES = [
+    ("wino2_fwd", "fwd", (2, 64, 6, 3), W64, 1, 1, {"residual": True}, {}, ["wino_conv_kernel"], ["wino4_conv_kernel"],
+     64 * 64 * 16),
+    ("wino2_dgrad", "dgrad", (2, 64, 6, 3), W64, 1, 1, {}, {}, ["wino_conv_kernel"], ["wino4_conv_kernel"], 64 * 64 * 16),
+    ("wino4_fwd", "fwd", (2, 64, 6, 4), W64, 1, 1, {}, {}, ["wino4_conv_kernel"], ["wino_conv_kernel"],
+     64 * 64 * 36 + 1024),
+    ("wino4_dgrad", "dgrad", (2, 64, 6, 4), W64, 1, 1, {"accumulate": True}, {}, ["wino4_conv_kernel"],
+     ["wino_conv_kernel"], 64 * 64 * 36 + 1024),
+    ("ksplit_fwd", "fwd", (2, 512, 2, 32), (64, 512, 1, 1), 1, 0, {}, {}, ["conv_fwd_kernel", "reduce_partials_kernel"],
+     [], 64 * 512 + 2 * (2 * 64 * 2 * 32)),
+    ("bf3_fwd_s2", "fwd", X_S2, W128S2, 2, 1, {}, {}, ["conv_s2_bf3_kernel"], ["conv_fwd_kernel"], 128 * 64 * 9 * 6 // 4),
+    ("bf3_wgrad_s2", "wgrad", X_S2, W128S2, 2, 1, {}, {}, ["conv_s2w_bf3_kernel", "reduce_partials_kernel"],
+     ["conv_wgrad_kernel"], 2 * 128 * 64 * 9),
+    ("splitk_wgrad_s2_pro", "wgrad", X_S2, W128S2, 2, 1, {"pro": True}, {}, ["conv_wgrad_kernel", "reduce_partials_kernel"],
+     ["conv_s2w_bf3_kernel"], 10 * 128 * 64 * 9),
+    ("lone_dgrad_s2", "dgrad", X_S2, W128S2, 2, 1, {"accumulate": True}, {}, ["conv_s2_dgrad_kernel"], [], 64 * 128 * 9),
+    ("parity_class_dgrad_s2", "dgrad", X_S2, W128S2, 2, 1, {}, {"CONV_S2": 0}, ["conv_fwd_kernel"],
+     ["conv_s2_dgrad_kernel"], 64 * 128 * 9),
+    ("wino_wgrad", "wgrad", (2, 64, 6, 8), W64, 1, 1, {}, {}, ["wino_wgrad_kernel", "reduce_partials_kernel"], [],
+     6 * 64 * 64 * 9),
+    ("wino_pad_wgrad", "wgrad", (2, 48, 6, 8), (64, 48, 3, 3), 1, 1, {}, {},
+     ["copy_rows_kernel", "wino_wgrad_kernel", "reduce_partials_kernel"], [], 2 * 64 * 48 + (6 + 1) * 64 * 64 * 9),
+    ("skinny3_wgrad", "wgrad", (2, 16, 4, 8), (64, 16, 3, 3), 1, 1, {"pro": True}, {},
+     ["conv_wgrad_3x3_skinny_kernel", "reduce_partials_kernel"], [], 8 * 64 * 16 * 9),
+    ("skinny1_wgrad", "wgrad", (2, 16, 2, 64), (64, 16, 1, 1), 1, 0, {}, {},
+     ["conv_wgrad_1x1_skinny_kernel", "reduce_partials_kernel"], ["conv_wgrad_kernel"], 2 * 64 * 16),
+    ("splitk_wgrad_nsplit_eq_ntiles", "wgrad", (2, 64, 2, 64), (64, 64, 1, 1), 1, 0, {}, {},
+     ["conv_wgrad_kernel", "reduce_partials_kernel"], [], 8 * 64 * 64),
+    ("direct_fwd", "fwd", (2, 1, 12, 16), (16, 1, 9, 3), (3, 1), (1, 1), {}, {}, ["conv_direct_fwd_kernel"], [], 0),
+    ("direct_wgrad", "wgrad", (2, 1, 12, 16), (16, 1, 9, 3), (3, 1), (1, 1), {}, {},
+     ["conv_direct_wgrad_rows_kernel", "reduce_partials_kernel"], [], 4 * 16 * 27),
+    ("conv5_row_dgrad", "dgrad", (2, 64, 3, 16), W64, 1, (0, 1), {}, {}, ["conv_fwd_kernel<1,3,1,0,16,1"],
+     ["reduce_partials_kernel"], 64 * 64 * 9),
+]
+SENTINEL = 0xA5
+
+
+@pytest.mark.parametrize("case", WS_CASES, ids=[c[0] for c in WS_CASES])
+def test_route_stays_inside_the_declared_workspace(ops, case):
+    """Every route on a workspace of exactly air_conv2d_ws_bytes(p) bytes cut from the middle of a sentinel-filled
+    buffer: the route's kernels run, the result holds the route's bound against fp64, no byte outside the slice
+    changes, and one byte less than the route's own need is refused before anything is written."""
+    import ctypes
+    from asvspoof2021_air_amd import _hip
+    from asvspoof2021_air_amd._hip import ci, csz, dptr, stream
+    cid, op, xs, wshape, st, pd, flags, opts, has, lacks, need = case
+    lib = _hip.lib()
+    d = ops._conv_desc(xs, wshape, st, pd)
+    B, Cin = xs[0], xs[1]
+    yshape = (B, wshape[0], d.Ho, d.Wo)
+    x, w, dy = synth_feat(xs, 1).cuda(), _weights(wshape, 2), synth_feat(yshape, 6).cuda()
+    sc = sh = extra = None
+    if flags.get("pro"):
+        sc, sh = (1.0 + 0.2 * synth_feat((Cin,), 3)).cuda(), (0.3 * synth_feat((Cin,), 4)).cuda()
+    if flags.get("residual") or flags.get("accumulate"):
+        extra = synth_feat(yshape if op == "fwd" else xs, 5).cuda()
+    null = ctypes.c_void_p(0)
+    oshape = {"fwd": yshape, "dgrad": tuple(xs), "wgrad": tuple(wshape)}[op]
+
+    def call(out, ws, nbytes):
+        wsp = ctypes.c_void_p(ws.data_ptr())
+        if op == "fwd":
+            return lib.air_conv2d_fwd_pre(ctypes.byref(d), dptr(x), dptr(w), null, dptr(out), dptr(sc, allow_none=True),
+                                          dptr(sh, allow_none=True), ci(1 if sc is not None else 0),
+                                          dptr(extra, allow_none=True), null, wsp, csz(nbytes), stream())
+        if op == "dgrad":
+            return lib.air_conv2d_dgrad_pre(ctypes.byref(d), dptr(dy), dptr(w), null, dptr(out),
+                                            dptr(extra, allow_none=True), wsp, csz(nbytes), stream())
+        return lib.air_conv2d_wgrad(ctypes.byref(d), dptr(x), dptr(dy), dptr(out), dptr(sc, allow_none=True),
+                                    dptr(sh, allow_none=True), ci(1 if sc is not None else 0), wsp, csz(nbytes), stream())
+
+    with _hip.options(**opts):
+        n = int(lib.air_conv2d_ws_bytes(ctypes.byref(d)))
+        assert n >= 4 * need + 256, (n, need)
+        guard = (n + 65535) // 65536 * 65536  # an overrun of up to the whole size again lands in the sentinel
+        buf = torch.full((guard + n + guard,), SENTINEL, dtype=torch.uint8, device="cuda")
+        ws = buf[guard:guard + n]
+        out = torch.full(oshape, 7.0, device="cuda")
+        rc, names = kernels_of(lambda: call(out, ws, n))
+        assert rc == 0, rc
+        check_route(names, has, lacks, None, None)
+        assert bool((buf[:guard] == SENTINEL).all()) and bool((buf[guard + n:] == SENTINEL).all()), \
+            "the route wrote outside air_conv2d_ws_bytes(p)"
+        if need > 0:
+            small = torch.full(oshape, 7.0, device="cuda")
+            assert call(small, ws, 4 * need - 1) == AIR_EWORKSPACE
+            torch.cuda.synchronize()
+            assert bool((small == 7.0).all()), "a refused call wrote its output"
+    if op == "fwd":
+        want = ref_fwd(x, w, st, pd, sc, sh)
+    elif op == "dgrad":
+        want = ref_dgrad(dy, w, tuple(xs), st, pd)
+    else:
+        want = ref_wgrad(x, dy, wshape, st, pd, sc, sh)
+    if extra is not None:
+        want = want + extra.double()
+    if any(base(k) == "wino_wgrad_kernel" for k in names):
+        rtol = WINO_WGRAD_RTOL
+    else:
+        rtol = wino_conv_bound() if is_wino(names) else STRICT["conv_rtol"]
+    close(out, want, rtol, "%s on an exact workspace" % cid)
 
 
 # ------------------------------------------------------------------------------------------------ coverage

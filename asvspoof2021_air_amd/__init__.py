@@ -9,5 +9,14 @@ behind the reference's Python module surface:
 
 All device arithmetic runs in hand-written gfx950 HIP kernels reached through
 the C-ABI in include/air_hip.h (libair_hip.so, loaded with ctypes).
+
+The GMM back-end (gmm.py) is exported here: ``from asvspoof2021_air_amd import DiagGMM, GMMBackend``.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):  # resolved on first use: importing the package stays as light as it was
+    if name in ("DiagGMM", "GMMBackend"):
+        from . import gmm
+        return getattr(gmm, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

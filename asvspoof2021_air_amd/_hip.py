@@ -112,7 +112,8 @@ def lib():
                      "air_conv1d_tap_pack_elems", "air_h_bn_ws_bytes", "air_h_conv1d_ws_bytes", "air_conv2d_fwd_stats_bytes", "air_conv2d_dgrad_bn_sums_bytes", "air_conv2d_dgrad_s2_pair_prepack_bytes", "air_h_conv1d_tap_stats_bytes", "air_h_conv1d_tap_bwd_sums_bytes", "air_h_conv1d_pointwise_stats_bytes",
                      "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes", "air_adv_heads_ws_bytes",
                      "air_eval_workspace_bytes", "air_eval_workspace_bytes_grouped", "air_pca_ws_bytes", "air_tsne_ws_bytes",
-                     "air_flac_workspace_bytes", "air_corpus_permutation_ws_bytes", "air_rawboost_ws_bytes"):
+                     "air_flac_workspace_bytes", "air_corpus_permutation_ws_bytes", "air_rawboost_ws_bytes",
+                     "air_gmm_ws_bytes", "air_gmm_params_doubles", "air_gmm_stats_doubles"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_size_t
     return _lib

@@ -294,3 +294,45 @@ def test_on_dataset_ensemble(models, loader, score_files, fused_file=None, metho
         os.makedirs(os.path.dirname(os.path.abspath(fused_file)), exist_ok=True)
         sf.write_fused(fused_file, [joined[i] for i in order], host[K * n:].numpy()[order])
     return n, result
+
+
+@torch.no_grad()
+def test_on_dataset_gmm(backend, loader, score_file, task="19eval", device="cuda", keep_dataset_labels=False, sync="end"):
+    """The score file of ``test_on_dataset`` for a ``gmm.GMMBackend``: the same loop over the same batches
+    (``(lfcc:(B,1,feat_len,60), audio_fn, tag, labels[, channel])`` for the '19' tasks, ``(lfcc, audio_fn)`` for the 2021
+    evaluation sets), the same ``format_score_line`` and the same label quirk; the value written is the back-end's
+    log-likelihood ratio (higher = bona fide).  The first item may also be (B, Lcap) PCM, optionally followed by a sixth
+    / third item with the int32 lengths: it then goes through the back-end's own front-end.  Pre-extracted features
+    count every frame of the row - padding frames included, as the networks see them.  ``sync`` as there; returns the
+    number of lines written."""
+    if sync not in ("batch", "end"):
+        raise ValueError("sync must be 'batch' or 'end', got %r" % (sync,))
+    os.makedirs(os.path.dirname(os.path.abspath(score_file)), exist_ok=True)
+    is19 = "19" in task
+    held, rows, n = None, [], 0
+    with open(score_file, "w") as fh:
+        for data in loader:
+            x, audio_fn = data[0].to(device), data[1]
+            labels = data[3] if is19 else None
+            if x.dim() == 2:
+                extra = 5 if is19 else 2
+                score = backend.score(x, data[extra] if len(data) > extra else None)
+            else:
+                feats = x.reshape(x.shape[0], x.shape[-2], x.shape[-1]).float()  # (B, feat_len, D): frame-major
+                score = backend.score_frames(feats, None, "btd")
+            keys = [(("spoof" if (int(labels[j]) if keep_dataset_labels else 0) else "bonafide") if is19 else None)
+                    for j in range(x.shape[0])]
+            if sync == "end":
+                if held is None:
+                    held = DeviceVector(torch.float32, score.device, (len(loader) if hasattr(loader, "__len__") else 64) * x.shape[0])
+                held.append(score)
+                rows.extend(zip(audio_fn, keys))
+                continue
+            for name, key, v in zip(audio_fn, keys, score.cpu().tolist()):
+                fh.write(format_score_line(name, v, key))
+                n += 1
+        if held is not None:
+            for (name, key), v in zip(rows, held.view().cpu().tolist()):
+                fh.write(format_score_line(name, v, key))
+                n += 1
+    return n

@@ -1420,6 +1420,64 @@ int air_corpus_gather(const air_corpus_view* c, const air_corpus_segment* seg, i
                       int hop, int Lcap, void* pcm, int* lengths, int64_t* labels, int64_t* tags, int64_t* channels,
                       int64_t* index, int* start, air_stream_t stream);
 
+/* ---------------------------------------------------------- GMM back-end ---
+ * A diagonal-covariance Gaussian mixture on feature frames: fp64 EM and log-likelihood scoring (the ASVspoof baselines
+ * B01/B02 are two such models, bona fide and spoof, scored by the log-likelihood ratio).  No reference counterpart;
+ * the arithmetic is scikit-learn 1.7's GaussianMixture(covariance_type="diag") from a given initialisation
+ * (_estimate_log_gaussian_prob, _estimate_gaussian_covariances_diag, _m_step).  This block is the specification;
+ * tests/gmm_oracle.py states it in numpy.
+ *
+ * A model is w (K), mu (K, D), var (K, D), all fp64.  Frames x are fp32 and are widened exactly.  With p = 1 / var:
+ *
+ *   lp[n,k]  = log w_k - 0.5 * (D log(2 pi) + sum_d mu^2 p + sum_d log var) + sum_d x (mu p) - 0.5 sum_d x^2 p
+ *   lse[n]   = logsumexp_k lp[n,k]                (max-shifted)
+ *   r[n,k]   = exp(lp[n,k] - lse[n])
+ *   S0[k] = sum_n r    S1[k,d] = sum_n r x    S2[k,d] = sum_n r x^2    LL = sum_n lse    Nf = number of frames
+ *   M-step:  nk = S0 + 10 * 2^-52;  mu = S1 / nk;  var = S2 / nk - mu^2 + reg_covar;  w = nk / sum_k nk;
+ *            lower_bound = LL / Nf
+ *
+ * score_samples = lse; a row's score is the mean of lse over its frames (NaN for a row without frames); an utterance's
+ * back-end score is mean lse_bona - mean lse_spoof.  An empty component ends at mu = 0, var = reg_covar.
+ *
+ * Frames: layout 0 is frame-major (B, Tcap, D) - (N, D) is B = 1 - and layout 1 the models' (B, D, Tcap).  n_frames is
+ * int32 (B) on the device or NULL (every row full): row b contributes the frames t < min(max(n_frames[b], 0), Tcap).
+ * Nothing else is read into the arithmetic: the other frames are replaced by zeros before they reach an MFMA and
+ * carry r = 0, so NaN padding changes nothing.  1 <= K <= 1024, 1 <= D <= 128, B * Tcap < 2^31; anything else is
+ * AIR_EUNSUPPORTED (layout outside {0, 1}, B or Tcap < 1: AIR_EINVAL) before any HIP call.
+ *
+ * air_gmm_prepare packs the model for the E-step into params (air_gmm_params_doubles(K, D) fp64): per tile of 16
+ * components the MFMA B operand [feature j][component], j < Dp: mu p, Dp <= j < 2 Dp: -0.5 p (Dp = D padded to 8, 32,
+ * 64 or 128, zeros in the padding), then the constants c_k (-inf for the padding components).
+ * stats is air_gmm_stats_doubles(K, D) = K + 2 K D + 2 fp64: S0 (K), S1 (K, D), S2 (K, D), LL, and Nf as int64 in the
+ * last 8 bytes.  air_gmm_accumulate ADDS this batch's sums to it (zero it to begin an iteration); calls accumulate in
+ * stream order.  The (N, K) responsibilities never reach memory: pass A leaves lse per frame (8 bytes) and one (LL,
+ * count) pair per tile of air_gmm_frame_tile() frames in ws; pass B recomputes the logits per (frame chunk x 64
+ * components) workgroup and keeps its 64 x 2 Dp sums in registers; pass C adds the per-chunk partials in chunk order.
+ * All products and sums are fp64 on v_mfma_f64_16x16x4_f64 where they are matrix products.  No atomics: the same call
+ * on the same stats gives the same bits.  No host synchronisation in accumulate, loglik or mstep.
+ * air_gmm_loglik: frame_ll (B * Tcap fp64, 0 for frames beyond a row's count) and / or row_ll (B fp64), either may be
+ * NULL; ws as for accumulate (only the lse part is used when frame_ll is NULL).
+ * air_gmm_mstep reads stats and writes w, mu, var and lower_bound (1 fp64) on the device.
+ * air_gmm_ws_bytes(n_frames_cap = B * Tcap, K, D): 0 for sizes the calls refuse; a smaller ws: AIR_EWORKSPACE. */
+int air_gmm_frame_tile(void);
+size_t air_gmm_params_doubles(int K, int D);
+size_t air_gmm_stats_doubles(int K, int D);
+size_t air_gmm_ws_bytes(int64_t n_frames_cap, int K, int D);
+int air_gmm_prepare(const double* w, const double* mu, const double* var, int K, int D, double* params,
+                    air_stream_t stream);
+int air_gmm_accumulate(const float* x, int layout, int B, int Tcap, const int* n_frames, const double* params, int K,
+                       int D, double* stats, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_gmm_loglik(const float* x, int layout, int B, int Tcap, const int* n_frames, const double* params, int K, int D,
+                   double* frame_ll, double* row_ll, void* ws, size_t ws_bytes, air_stream_t stream);
+int air_gmm_mstep(const double* stats, int K, int D, double reg_covar, double* w, double* mu, double* var,
+                  double* lower_bound, air_stream_t stream);
+/* Measurement instrumentation, not part of the interface (like the air_debug_* entries above: it may change or go
+ * without an ABI bump; only tools/bench_gmm.py calls it): nblocks workgroups of four waves, each wave `iters` rounds of four independent
+ * v_mfma_f64_16x16x4_f64 (2048 flop each) with no memory traffic in the loop; out gets nblocks * 256 fp64.  The rate it
+ * reaches is the measured fp64 matrix peak tools/bench_gmm.py holds the kernels against.  nblocks <= 65536,
+ * iters <= 2^24. */
+int air_debug_mfma_f64_probe(int nblocks, int iters, double* out, air_stream_t stream);
+
 /* ------------------------------------------------------------ optimiser ---
  * torch.optim.Adam as configured at main_train.py:175-176 (coupled L2 weight
  * decay) and torch.optim.SGD(lr) (main_train.py:272), over flat fp32 buffers.

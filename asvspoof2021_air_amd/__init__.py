@@ -10,7 +10,8 @@ behind the reference's Python module surface:
 All device arithmetic runs in hand-written gfx950 HIP kernels reached through
 the C-ABI in include/air_hip.h (libair_hip.so, loaded with ctypes).
 
-The GMM back-end (gmm.py) is exported here: ``from asvspoof2021_air_amd import DiagGMM, GMMBackend``.
+The GMM back-end (gmm.py) is exported here: ``from asvspoof2021_air_amd import DiagGMM, GMMBackend``, and so is the
+CQCC front-end (feature_extraction.py): ``from asvspoof2021_air_amd import CQCC``.
 """
 __version__ = "0.1.0"
 
@@ -19,4 +20,7 @@ def __getattr__(name):  # resolved on first use: importing the package stays as 
     if name in ("DiagGMM", "GMMBackend"):
         from . import gmm
         return getattr(gmm, name)
+    if name == "CQCC":
+        from . import feature_extraction
+        return feature_extraction.CQCC
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

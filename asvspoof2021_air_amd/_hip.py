@@ -113,7 +113,7 @@ def lib():
                      "air_h_conv1d_tap_wgrad_ws_bytes", "air_conv_narrow_wgrad_ws_bytes", "air_adv_heads_ws_bytes",
                      "air_eval_workspace_bytes", "air_eval_workspace_bytes_grouped", "air_pca_ws_bytes", "air_tsne_ws_bytes",
                      "air_flac_workspace_bytes", "air_corpus_permutation_ws_bytes", "air_rawboost_ws_bytes",
-                     "air_gmm_ws_bytes", "air_gmm_params_doubles", "air_gmm_stats_doubles"):
+                     "air_gmm_ws_bytes", "air_gmm_params_doubles", "air_gmm_stats_doubles", "air_cqcc_plan_bytes", "air_cqcc_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_size_t
     return _lib

@@ -365,3 +365,103 @@ class Melspec(_Spectral):
 
     def forward(self, x):
         return self.forward_batch(x[:1])[0]
+
+
+class CQCC(_FrontEnd):
+    """CQCC(sr=16000, bins_per_octave=96, n_octaves=9, hop=160, n_coef=20, d=16, eps=2**-52): constant-Q cepstral
+    coefficients, the reference's second feature (``--feat CQCC``), on the kernels of csrc/cqcc.hip.  The reference
+    ships no CQCC code: the feature is defined by the formulas of include/air_hip.h ("CQCC front-end") and pinned by a
+    numpy fp64 oracle; parity with the challenge's MATLAB toolbox is not claimed ("CQCC").
+
+    ``forward(x:(B, L)) -> (B, 1 + L // hop, 3 * n_coef)``, columns [static, delta, delta-delta] - the shape ``LFCC``
+    feeds to the models and the GMMs; ``forward_padded`` / ``forward_ragged`` as in the other front-ends ('repeat' and
+    'zero' padding; 'silence' is LFCC's and raises ValueError); ``forward_spectrum`` returns the (B, T, K) log power
+    the cepstra are projected from.  fp32 or int16 PCM; ``x`` is never modified.  Built: 96 bins per octave, up to 9
+    octaves, hop <= 160, n_coef <= 32."""
+    NAME = "CQCC"
+    with_emphasis = False
+    mutate_input = False
+
+    def __init__(self, sr=16000, bins_per_octave=96, n_octaves=9, hop=160, n_coef=20, d=16, eps=2.0 ** -52):
+        super().__init__()
+        if bins_per_octave != 96 or not 1 <= n_octaves <= 9 or not 1 <= hop <= 160 or not 1 <= n_coef <= 32:
+            raise NotImplementedError("CQCC is built for 96 bins per octave, 1..9 octaves, hop <= 160 and n_coef <= 32, "
+                                      "got %s" % ((bins_per_octave, n_octaves, hop, n_coef),))
+        if d < 1 or eps < 0:
+            raise ValueError("CQCC needs d >= 1 and eps >= 0")
+        self.sr, self.bins_per_octave, self.n_octaves, self.n_coef, self.d, self.eps = (
+            sr, bins_per_octave, n_octaves, n_coef, d, eps)
+        self.fs = hop  # the hop, under the name the other front-ends give it
+
+    @property
+    def out_dim(self):
+        return 3 * self.n_coef
+
+    @property
+    def n_bins(self):
+        return self.bins_per_octave * self.n_octaves
+
+    def _flags(self):
+        return 0
+
+    def _plan_id(self, device):
+        return (str(device), self.n_octaves, self.fs, self.n_coef, self.d, self.eps)
+
+    def _plan_build(self, lib):
+        import ctypes
+        host = torch.zeros(lib.air_cqcc_plan_bytes(), dtype=torch.uint8)
+        _hip.check(lib.air_cqcc_plan_build(_hip.ci(self.bins_per_octave), _hip.ci(self.n_octaves), _hip.ci(self.fs),
+                                           _hip.ci(self.n_coef), _hip.ci(self.d), ctypes.c_double(self.eps),
+                                           _hip.hptr(host, torch.uint8)), "air_cqcc_plan_build")
+        return host
+
+    def _check(self, x, padding="repeat"):
+        mode = pad_mode_id(padding)
+        if mode == 2:
+            raise ValueError("padding='silence' prepends an LFCC frame (dataset.py:13-16) and is served by LFCC only; "
+                             "CQCC pads with 'repeat' or 'zero' (AIR_EUNSUPPORTED)")
+        self._check_x(x)
+        return mode
+
+    def _geometry(self):
+        return _hip.ci(self.n_octaves), _hip.ci(self.fs), _hip.ci(self.n_coef)
+
+    def _workspace(self, lib, B, Lcap, device):
+        """Scratch of one call (pyramid, log spectrum, statics): a function of (B, Lcap) only, taken from the stream's
+        growing buffer like every other op's, so a captured step points into it."""
+        from . import ops
+        nbytes = lib.air_cqcc_ws_bytes(B, Lcap, *self._geometry())
+        ws = ops.workspace(nbytes, device)
+        return _hip.dptr(ws, torch.uint8), _hip.csz(nbytes)
+
+    def _call_dense(self, lib, src, B, L, out, plan, flags):
+        _hip.check(lib.air_cqcc_fwd(*pcm_pointers(src), B, L, out, plan, *self._geometry(),
+                                    *self._workspace(lib, B, L, src.device), _hip.stream()), "air_cqcc_fwd")
+
+    def _call_padded(self, lib, rows, lengths, tail, mode, device):
+        out, feat_len, start, plan, _flags, pad = tail
+        _hip.check(lib.air_cqcc_fwd_ragged(*rows, _hip.dptr(lengths, torch.int32, True), out, feat_len, start, plan,
+                                           *self._geometry(), pad, *self._workspace(lib, rows[2], rows[3], device),
+                                           _hip.stream()), "air_cqcc_fwd_ragged")
+
+    def forward(self, x):
+        self._check(x)
+        return self._dense(x)[0]
+
+    def forward_spectrum(self, x, lengths=None):
+        """(B, L) -> (B, 1 + L // hop, K) log power S[k, t] = log(|X|^2 + eps), K = bins_per_octave * n_octaves, bin 0
+        the lowest.  ``lengths``: the batch is ragged; frames at or behind a row's own count are zero."""
+        self._check(x)
+        B, Lcap = x.shape
+        lib = _hip.lib()
+        if lengths is not None:
+            lengths = device_lengths(lengths, B, Lcap, x.device)
+        src = _pcm_source(x)
+        shape = (B, 1 + Lcap // self.fs, self.n_bins)
+        out = (torch.empty if lengths is None else torch.zeros)(shape, device=x.device, dtype=torch.float32)
+        _hip.check(lib.air_cqcc_spectrum(*pcm_pointers(src), _hip.ci(B), _hip.ci(Lcap),
+                                         _hip.dptr(lengths, torch.int32, True), _hip.dptr(out),
+                                         _hip.dptr(self.plan(x.device), torch.uint8), *self._geometry(),
+                                         *self._workspace(lib, _hip.ci(B), _hip.ci(Lcap), x.device), _hip.stream()),
+                   "air_cqcc_spectrum")
+        return out

@@ -188,6 +188,64 @@ int air_spec_fwd_ragged(int kind, const float* pcm, const int16_t* pcm16, int B,
                         float* out, int feat_len, const int* start_dev, const void* plan_dev, int flags, int pad_mode,
                         air_stream_t stream);
 
+/* ------------------------------------------------------- CQCC front-end --
+ * Constant-Q cepstral coefficients, the reference's second feature (--feat CQCC).  The reference ships no CQCC code,
+ * so the feature is DEFINED by these formulas (csrc/cqcc.hip; tests/cqcc_oracle.py restates them in numpy fp64);
+ * parity with the challenge's MATLAB toolbox is not claimed.
+ *
+ *   sr 16000, B = bins_per_octave 96, O = n_octaves 9, hop 160, n_coef 20 (c0 included), d 16, eps 2^-52.
+ *   fmax = sr / 2, fmin = fmax / 2^O, K = B O bins at f_k = fmin 2^(k / B); Q = 1 / (2^(1/B) - 1).
+ *   Octave o = O - 1 - k / B (integer division); o = 0 is the top one.
+ *
+ *   1. Pyramid.  Level 0 is the row (16-bit PCM as s / 32768, no pre-emphasis), L_0 = L samples.  Level s + 1 has
+ *      L_{s+1} = ceil(L_s / 2) samples, x_{s+1}[n] = sum_j h[j] x_s[2 n + j - (J - 1) / 2], zeros outside [0, L_s).
+ *      h: J = 47 taps, h[j] = 0.5 sinc((j - 23) / 2) kaiser_47(beta = 16)[j], scaled to unit sum: a half-band low-pass
+ *      whose stopband from 3 R / 8 is below -150 dB (the oracle's test measures it), i.e. below fp32 roundoff.
+ *      Octaves 0 and 1 are analysed at level 0, octave o >= 2 at level o - 1: every band but the top one lies in
+ *      [R/8, R/4) of its own rate R, where h is flat and what folds onto it comes from beyond 3 R / 8.
+ *   2. Atoms.  At rate R the bin at f has N = 2 floor(Q R / (2 f)) + 1 samples, a symmetric Hann window w over them
+ *      (w[n] = 0.5 - 0.5 cos(2 pi n / (N - 1))), and
+ *        X[k, t] = (1 / sum w) sum_n w[n] x_s[c + n - (N-1)/2] exp(-2 pi i f (n - (N-1)/2) / R),  c = floor(t hop / 2^s),
+ *      zeros outside the level.  In f / R the atoms of all octaves >= 1 are one table (N = 555 .. 1103), the top
+ *      octave's a second (N = 277 .. 551); both are formed in fp64 and rounded once.
+ *   3. Frames.  T_b = 1 + L_b / hop.
+ *   4. S[k, t] = log(|X|^2 + eps).
+ *   5. S is read by linear interpolation in k at B log2(g_m / fmin), g_m = fmin (1 + m / d), m < M = 1 + floor(d
+ *      (f_{K-1} / fmin - 1)) (8118 at the defaults); the orthonormal DCT-II of those M values gives c_q, q < n_coef.
+ *      The plan holds the product of both steps, one (n_coef x K) matrix formed in fp64.
+ *   6. Delta and delta-delta as in the LFCC front-end (x[t + 1] - x[t - 1] with the edge frames repeated, twice), over
+ *      the row's own frames.  Columns [static, delta, delta-delta], D = 3 n_coef.
+ *
+ * Built: bins_per_octave 96, n_octaves 1 .. 9, hop 1 .. 160, n_coef 1 .. 32 (anything else: AIR_EUNSUPPORTED).  The
+ * plan blob (air_cqcc_plan_bytes() bytes, built on the host, uploaded by the caller): int32[12] tag, O, hop, n_coef, K,
+ * J, half-lengths of the two tables, d, M, 0, 0; float[4] eps, 0, 0, 0; float[64] h; float[32][864] P (rows of K
+ * floats, packed); float[576][192] and float[1120][192] atom tables, row = tap, column 32 (bin / 16) + 16 part + bin % 16
+ * with part 0 = real, 1 = imaginary.  n_octaves, hop and n_coef travel as arguments too (they size the launches); a
+ * plan that disagrees with them writes nothing. */
+size_t air_cqcc_plan_bytes(void);
+int air_cqcc_plan_build(int bins_per_octave, int n_octaves, int hop, int n_coef, int d, double eps,
+                        void* plan_host_out);
+/* K = bins_per_octave * n_octaves (AIR_EUNSUPPORTED outside what is built). */
+int air_cqcc_n_bins(int bins_per_octave, int n_octaves);
+/* Scratch of one call, a function of (B, Lcap) and the geometry only: the pyramid levels, the (B, T, K) log spectrum
+ * (89 MB at 64 x 64 000 samples) and the (B, T, n_coef) statics.  0 for a geometry that is not built. */
+size_t air_cqcc_ws_bytes(int B, int Lcap, int n_octaves, int hop, int n_coef);
+/* Exactly one of pcm (B, L) fp32 / pcm16 is non-NULL; neither is modified.  out: (B, 1 + L / hop, 3 n_coef).  No host
+ * synchronisation; every sum in a fixed order, no atomics. */
+int air_cqcc_fwd(const float* pcm, const int16_t* pcm16, int B, int L, float* out, const void* plan_dev,
+                 int n_octaves, int hop, int n_coef, void* ws, size_t ws_bytes, air_stream_t stream);
+/* Rows of L_b = clamp(lengths_dev[b], 1, Lcap) samples (NULL: Lcap); no sample at index >= L_b is read, and row b is,
+ * bit for bit, what the dense call gives for it alone.  feat_len <= 0: out is (B, 1 + Lcap / hop, 3 n_coef) and only
+ * the first T_b frames of row b are written; otherwise out is (B, 3 n_coef, feat_len), padded / chopped as in
+ * air_spec_fwd_ragged (AIR_PAD_REPEAT, AIR_PAD_ZERO; AIR_PAD_SILENCE: AIR_EUNSUPPORTED). */
+int air_cqcc_fwd_ragged(const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev, float* out,
+                        int feat_len, const int* start_dev, const void* plan_dev, int n_octaves, int hop, int n_coef,
+                        int pad_mode, void* ws, size_t ws_bytes, air_stream_t stream);
+/* Step 4 alone: out is (B, 1 + Lcap / hop, K), the first T_b frames of row b written (lengths_dev may be NULL). */
+int air_cqcc_spectrum(const float* pcm, const int16_t* pcm16, int B, int Lcap, const int* lengths_dev, float* out,
+                      const void* plan_dev, int n_octaves, int hop, int n_coef, void* ws, size_t ws_bytes,
+                      air_stream_t stream);
+
 /* --------------------------------------------------------------- conv2d --
  * Replaces nn.Conv2d forward/backward as used by resnet.py:131,56-61,140
  * (bias=False everywhere).  NCHW fp32.  Implicit GEMM on f32 MFMA.
